@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Benchmark of the quantum-cartpole env.step() hot path (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config metric]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config metric] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (`roofline` from the HIP events of
+those same steps). --full adds what takes work of its own: the CPU baseline and the committed profiles' measured
+HBM traffic / executed flop counts for this library build. --dump-outputs DIR writes the last timed step's outputs
+(and a fixed sample of the state it left) as .npy files; inputs depend on the arguments alone, so two builds can
+be compared output for output.
 
 One bench "step" = one RL control step of the whole batch: every env advances one control
 interval (80 physics steps for the IHO, IHO/main_parallel.py:113-118) with its own discrete action,
@@ -43,7 +49,13 @@ def parse():
     ap.add_argument("--config", default="metric")
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: the config's)")
     ap.add_argument("--sub-steps", type=int, default=0, help="physics steps per bench step (default: control interval)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the plain run's result line: the CPU baseline (a child process, --cpu-seconds) and "
+                         "the committed profiles' measured HBM traffic / executed flops in `roofline`")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (and the state it left) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--cpu-threads", type=int, default=0, help="0: every usable host core (affinity / cgroup quota)")
     ap.add_argument("--launch-timeout", type=float, default=0.0,
@@ -250,8 +262,38 @@ def psi_digests(psi, chunk: int):
     return [hashlib.sha256(h[i:i + chunk].tobytes()).hexdigest()[:16] for i in range(0, h.shape[0], chunk)]
 
 
+DUMP_BUDGET = 60_000_000   # bytes of .npy payload of one run, all ranks together (--dump-outputs)
+
+
+def dump_outputs(outdir: str, out: dict, psi, suffix: str = "", ranks: int = 1):
+    """--dump-outputs: what the last timed step handed its caller — the step's result dict (observations, Fail /
+    termination steps) whole and the state it advanced in place, psi, for a fixed sample of envs (RandomState(12345)'s
+    permutation of the batch, sorted; every env when they fit the budget) — as float64 .npy files (float32 for a
+    complex64 state; complex values as [..., 2] = re, im). psi_envs.npy holds the sampled env indices."""
+    import numpy as np
+    import torch
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {}
+    for name, t in out.items():
+        if t is not None:
+            arrays[name] = t.detach().cpu().numpy().astype(np.float64)
+    left = DUMP_BUDGET // ranks - sum(a.nbytes for a in arrays.values())
+    B = psi.shape[0]
+    per_env = psi[0].numel() * psi.element_size() + 8
+    n = int(max(1, min(B, left // per_env)))
+    idx = np.sort(np.random.RandomState(12345).permutation(B)[:n])
+    sample = psi[torch.from_numpy(idx).to(psi.device)].cpu()
+    arrays["psi"] = torch.view_as_real(sample).numpy() if sample.is_complex() else sample.numpy()
+    arrays["psi_envs"] = idx.astype(np.float64)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(outdir, name + suffix + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     args = parse()
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
     world = int(os.environ.get("WORLD_SIZE", "0") or 0)
     # under a launcher (WORLD_SIZE set, world 1 included) the ranks form an RCCL group; a plain
     # `python bench.py` (N = 1) runs without one
@@ -333,6 +375,8 @@ def main():
     world_seen = 1
     rccl = None
     digests = psi_digests(psi, args.digest_envs) if args.digest_envs else None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, psi, f"_rank{rank}" if world > 1 else "", world)
     if use_dist:
         t = coll(t)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -398,8 +442,8 @@ def main():
         "rl_steps_per_s": value / ph.control_interval,
     }
     # HBM traffic per launch measured by rocprofv3 PMC (FETCH_SIZE x2 + WRITE_SIZE, tools/prof_summary.py)
-    # for this same workload, when a committed profile exists
-    prof = latest_profile(res["config"]["workload"], sha)
+    # for this same workload, when a committed profile exists (--full: a plain run reads no profile)
+    prof = latest_profile(res["config"]["workload"], sha) if args.full else None
     if prof is not None:
         res["roofline"]["traffic"] = prof["hbm_bytes_per_launch"]
         res["roofline"]["traffic_unit"] = "bytes/launch (rocprofv3 PMC, profiles/%s_summary.json)" % prof["tag"]
@@ -409,14 +453,14 @@ def main():
     # per-element count of SURVEY §8d
     b = res["roofline"]["binding"]
     b["executed_flops_per_elem"] = b["executed_frac"] = b["executed_achieved"] = None
-    sq = latest_sq(res["config"]["workload"], sha)
+    sq = latest_sq(res["config"]["workload"], sha) if args.full else None
     if sq is not None:
         fe = executed_flops_per_elem(sq, fp32)
         if fe:
             ex = fe * N * per_launch_units / (kern_ms * 1e-3)
             b.update(executed_flops_per_elem=fe, executed_achieved=ex / 1e12, executed_frac=ex / peak_valu,
                      executed_source="profiles/%s_sq.json" % sq["tag"])
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             res["cpu_baseline"] = cpu_baseline(args.config, args.cpu_seconds, args.cpu_threads)
         except Exception as e:  # the baseline is reported, never fatal

@@ -4,7 +4,8 @@ run one after another (python -m tests.bench_children <outdir>); tests/test_gpu_
   rccl    bench.py's rank body under a launcher's environment at WORLD_SIZE = 1: an RCCL communicator of one rank
   share2  `bench.py --gpus 2` through bench.py's own launcher with QCART_BENCH_SHARE_DEVICE=1: both ranks on
           device 0, gloo carrying the collectives (the N-rank path rehearsed on a one-GPU lease)
-  whole1  a plain one-rank run of the two ranks' envs together, for the shard-digest comparison
+  whole1  a plain one-rank run of the two ranks' envs together, for the shard-digest comparison; it also writes
+          its last step's outputs (--dump-outputs <outdir>/whole1_dump)
   trun2   the driver's own launch, `python -m torch.distributed.run --nproc-per-node 2 ... bench.py --gpus 2`, with
           QCART_BENCH_SHARE_DEVICE=1 (both ranks on device 0, gloo)
 
@@ -22,7 +23,7 @@ BATCH = 512          # envs per rank
 COMMON = ["--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
 
 
-def runs():
+def runs(outdir: str):
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port = sk.getsockname()[1]
@@ -35,7 +36,8 @@ def runs():
         [bench, "--gpus", "1", "--batch", str(BATCH)] + COMMON
     yield "share2", dict(base, QCART_BENCH_SHARE_DEVICE="1"), \
         [bench, "--gpus", "2", "--batch", str(BATCH), "--digest-envs", str(BATCH), "--launch-timeout", "240"] + COMMON
-    yield "whole1", base, [bench, "--gpus", "1", "--batch", str(2 * BATCH), "--digest-envs", str(BATCH)] + COMMON
+    yield "whole1", base, [bench, "--gpus", "1", "--batch", str(2 * BATCH), "--digest-envs", str(BATCH),
+                           "--dump-outputs", os.path.join(outdir, "whole1_dump")] + COMMON
     with socket.socket() as sk:
         sk.bind(("127.0.0.1", 0))
         port2 = sk.getsockname()[1]
@@ -59,7 +61,7 @@ def _kill_current(*_):
 
 def main(outdir: str) -> int:
     signal.signal(signal.SIGTERM, _kill_current)
-    for name, env, argv in runs():
+    for name, env, argv in runs(outdir):
         with open(os.path.join(outdir, name + ".log"), "w") as log:
             p = subprocess.Popen([sys.executable, "-u"] + argv, cwd=ROOT, env=env, stdout=log,
                                  stderr=subprocess.STDOUT, start_new_session=True)

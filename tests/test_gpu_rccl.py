@@ -84,6 +84,29 @@ def test_rank_shards_equal_the_one_rank_run_bitwise(request):
 
 
 @pytest.mark.timeout(1000)
+def test_dumped_outputs_are_the_last_timed_steps(request):
+    """--dump-outputs of the one-rank run: every result of the last step as float64 .npy, and the state it left —
+    all 2B envs fit the budget here, so the dumped psi hashes to the psi_digests of the same run's result line."""
+    import hashlib
+
+    import numpy as np
+    outdir = _wait(request)
+    res = _result(outdir, "whole1")
+    d = os.path.join(outdir, "whole1_dump")
+    got = {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+    assert set(got) == {"fail_step", "obs", "psi", "psi_envs"}
+    assert all(a.dtype == np.float64 for a in got.values())
+    n = 2 * BATCH
+    assert np.array_equal(got["psi_envs"], np.arange(n, dtype=np.float64))
+    assert got["psi"].shape == (n, res["config"]["seq_len"], 2)
+    assert got["obs"].shape == (n, 5) and np.isfinite(got["obs"]).all()
+    assert got["fail_step"].shape == (n,) and (got["fail_step"] >= 0).all()
+    psi = np.ascontiguousarray(got["psi"]).view(np.complex128)[..., 0]
+    dig = [hashlib.sha256(psi[i:i + BATCH].tobytes()).hexdigest()[:16] for i in range(0, n, BATCH)]
+    assert dig == res["psi_digests"]
+
+
+@pytest.mark.timeout(1000)
 def test_torchrun_launch_on_one_device(request):
     """The driver's own N-rank launch (python -m torch.distributed.run --nproc-per-node 2 ... bench.py --gpus 2): world
     2, one JSON line from rank 0, the same shard digests as bench.py's own launcher."""

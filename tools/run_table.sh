@@ -15,7 +15,7 @@ for spec in "C1:1:30:30" "C2:4096:30:30" "C3:16384:3:1" "C4:8192:3:1" "C5:32768:
       > "gpurun_out/rt_prof_$cfgname.txt" 2>&1; rc=$?
   echo "$cfgname profile rc=$rc"; [ $rc -eq 0 ] || exit $rc
   cd "$ROOT"
-  timeout -k 10 300 python bench.py --config "$cfgname" --batch "$b" --steps "$st" --warmup "$wu" --cpu-seconds 6 \
+  timeout -k 10 300 python bench.py --full --config "$cfgname" --batch "$b" --steps "$st" --warmup "$wu" --cpu-seconds 6 \
       > "gpurun_out/rt_$cfgname.log" 2>&1; rc=$?
   echo "$cfgname bench rc=$rc $(grep -o '"value": [0-9.e+]*' gpurun_out/rt_$cfgname.log | head -1)"
   [ $rc -eq 0 ] || exit $rc
