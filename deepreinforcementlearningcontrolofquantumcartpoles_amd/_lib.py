@@ -42,6 +42,9 @@ EXPORTS = (
     "qc_server_create", "qc_server_run", "qc_server_stop", "qc_server_stats", "qc_server_timing", "qc_server_resident",
     "qc_server_last_error",
     "qc_server_destroy", "qc_env_tail",
+    "qc_learner_create", "qc_learner_destroy", "qc_learner_last_error", "qc_learner_set_stream",
+    "qc_learner_noise_len", "qc_learner_load", "qc_learner_layers", "qc_learner_update", "qc_learner_set_lr",
+    "qc_learner_stats", "qc_learner_grads", "qc_learner_apply",
 )
 
 
@@ -122,6 +125,33 @@ class QcDqnLayer(ctypes.Structure):
         ("weight_norm", ctypes.c_void_p),
         ("sigma_w", ctypes.c_void_p),
         ("sigma_b", ctypes.c_void_p),
+    ]
+
+
+class QcLearnerParams(ctypes.Structure):
+    _fields_ = [
+        ("data_length", ctypes.c_int32),
+        ("n_actions", ctypes.c_int32),
+        ("batch_size", ctypes.c_int32),
+        ("backup_period", ctypes.c_int32),
+        ("gamma", ctypes.c_double),
+        ("lr", ctypes.c_double),
+        ("alive_reward", ctypes.c_double),
+        ("failing_reward", ctypes.c_double),
+        ("seed", ctypes.c_uint64),
+    ]
+
+
+class QcLearnerStats(ctypes.Structure):
+    _fields_ = [
+        ("updates", ctypes.c_int64),
+        ("step", ctypes.c_int64),
+        ("nonfinite", ctypes.c_int64),
+        ("l1", ctypes.c_double),
+        ("l2", ctypes.c_double),
+        ("lr", ctypes.c_double),
+        ("backup_counter", ctypes.c_int32),
+        ("launches_per_update", ctypes.c_int32),
     ]
 
 
@@ -272,6 +302,20 @@ def lib() -> ctypes.CDLL:
     L.qc_replay_rebuild.argtypes = [vp]
     L.qc_replay_stats.argtypes = [vp, P(QcReplayStats)]
     L.qc_replay_buffers.argtypes = [vp, P(vp), P(vp)]
+    L.qc_learner_create.argtypes = [P(QcLearnerParams), ctypes.c_int, P(vp)]
+    L.qc_learner_destroy.argtypes = [vp]
+    L.qc_learner_destroy.restype = None
+    L.qc_learner_last_error.argtypes = [vp]
+    L.qc_learner_last_error.restype = ctypes.c_char_p
+    L.qc_learner_set_stream.argtypes = [vp, vp]
+    L.qc_learner_noise_len.argtypes = [vp]
+    L.qc_learner_load.argtypes = [vp, P(QcDqnLayer)]
+    L.qc_learner_layers.argtypes = [vp, ctypes.c_int, P(QcDqnLayer)]
+    L.qc_learner_update.argtypes = [vp, vp, vp, vp, u64, vp, vp]
+    L.qc_learner_set_lr.argtypes = [vp, d]
+    L.qc_learner_stats.argtypes = [vp, P(QcLearnerStats)]
+    L.qc_learner_grads.argtypes = [vp, P(QcDqnLayer)]
+    L.qc_learner_apply.argtypes = [vp, P(QcDqnLayer)]
     if isinstance(L, _Tolerant):
         L = L.lib
     for name in EXPORTS:
@@ -309,6 +353,13 @@ def check_actor(rc: int, handle=None) -> int:
 def check_mactor(rc: int, handle=None) -> int:
     if rc < 0:
         msg = lib().qc_mactor_last_error(handle)
+        raise QCartError(rc, msg.decode() if msg else "")
+    return rc
+
+
+def check_learner(rc: int, handle=None) -> int:
+    if rc < 0:
+        msg = lib().qc_learner_last_error(handle)
         raise QCartError(rc, msg.decode() if msg else "")
     return rc
 

@@ -21,19 +21,15 @@
 
 #include "../../include/qcart.h"
 #include "qcart_kernels.hpp"
+#include "qcart_mfma.hpp"
 
 namespace qcart {
 namespace actor {
 
-constexpr int kE = 32;                 // envs per workgroup (one MFMA column block)
+using namespace qcart::mfma;          // kE, f32x16, tiles / ksteps, gemm_tile, drow (qcart_mfma.hpp)
 constexpr int kH1 = 512, kH2 = 256, kH3 = 256;
 constexpr int kMaxIn = 512;            // data_length limit (LDS: [in][32] fp32 within 64 KiB)
 constexpr int kThreads = 256;
-using f32x16 = float __attribute__((ext_vector_type(16)));
-
-// fragment buffer of one [O][K] matrix: tiles of 32 outputs x K/2 steps x 64 lanes
-__host__ __device__ constexpr int tiles(int O) { return (O + 31) / 32; }
-__host__ __device__ constexpr int ksteps(int K) { return (K + 1) / 2; }
 
 struct Layer {
     const float* u;      // fragments of the (effective) weight
@@ -60,43 +56,6 @@ struct ActArgs {
     const float* h_in;
     int64_t h_ld;
 };
-
-// acc += A_frag(W) . X  over `steps` k-steps (X: LDS [k][32]; lane reads X[2s + (lane>>5)][lane&31]).
-// The weight fragments come from L2: batches of kP steps, the next batch's loads issued before the
-// current batch's MFMAs (kP x 64 cycles of MFMA cover the L2 latency at one wave per SIMD).
-constexpr int kP = 16;
-__device__ __forceinline__ void gemm_tile(f32x16& acc, const float* __restrict__ wf, const float* x, int steps,
-                                          int lane) {
-    const float* xl = x + (lane >> 5) * kE + (lane & 31);
-    const float* wl = wf + lane;
-    const int full = steps / kP * kP;
-    f32x16 acc1 = {};   // second accumulator chain (odd steps): halves the dependent-MFMA chain
-    float a[kP];
-    if (full > 0) {
-#pragma unroll
-        for (int u = 0; u < kP; ++u) a[u] = wl[u * 64];
-    }
-    for (int s = 0; s < full; s += kP) {
-        float an[kP];
-        const int sn = s + kP < full ? s + kP : s;   // last batch: harmless reload of the same fragments
-#pragma unroll
-        for (int u = 0; u < kP; ++u) an[u] = wl[(sn + u) * 64];
-        __builtin_amdgcn_sched_barrier(0);   // keep the next batch's loads ahead of this batch's MFMAs
-#pragma unroll
-        for (int u = 0; u < kP; u += 2) {
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], xl[(s + u) * 2 * kE], acc, 0, 0, 0);
-            acc1 = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u + 1], xl[(s + u + 1) * 2 * kE], acc1, 0, 0, 0);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int u = 0; u < kP; ++u) a[u] = an[u];
-    }
-    for (int s = full; s < steps; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(wl[s * 64], xl[s * 2 * kE], acc, 0, 0, 0);
-    acc += acc1;
-}
-
-// D-tile element r of this lane: output row (within the tile) and env column
-__device__ __forceinline__ int drow(int r, int lane) { return (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5); }
 
 __device__ __forceinline__ float noise_at(const ActArgs& a, int f, int64_t e) {
     return a.noise[(int64_t)f * a.noise_ld + e];
@@ -278,8 +237,8 @@ __global__ __launch_bounds__(1024) void k_actor_prep(const float* W, const float
     const float sc = g ? (float)((double)g[0] / sqrt(part[0])) : 1.f;
     const int T = tiles(O), S = ksteps(Kpad);
     for (int i = threadIdx.x; i < T * S * 64; i += 1024) {
-        const int l = i & 63, s = (i >> 6) % S, t = (i >> 6) / S;
-        const int o = t * 32 + (l & 31), k = split ? s + (l >> 5) * S : 2 * s + (l >> 5);
+        int o, k;
+        frag_ok(i, S, split, o, k);
         frag[i] = (o < O && k < K) ? W[(size_t)o * K + k] * sc : 0.f;
     }
     if (bias_pad)

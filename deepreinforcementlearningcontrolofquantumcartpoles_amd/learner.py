@@ -1,0 +1,208 @@
+"""Device DQN learner: the reference's TrainDQN.__call__ with its LaProp optimizer on the device.
+
+The reference learns in one process that samples `batch_size` transitions from the prioritized memory,
+evaluates direct_DQN three times (online on the next and previous states, target on the next states),
+backpropagates the importance-weighted TD loss and takes one LaProp step (inverted harmonic
+oscillator/RL.py:159-232, optimizer.py). `DQNLearner` does one such update in eight HIP launches
+(csrc/qcart_learner.hip, `qc_learner_update`) without leaving the device:
+
+    learner = DQNLearner(net.state_dict(), batch_size=512, lr=4e-4)
+    while training:
+        ...                                   # env.step / memory.store_xp, see BatchedEnv / PrioritizedReplay
+        for _ in range(n_learn):
+            learner.step(memory)              # obtain_sample -> update -> batch_update
+        learner.push(actor)                   # device-to-device weight push into a DQNActor
+
+`batch_size` must be a multiple of 128 (at most 4096): the learner implements FactorizedNoisy's batched
+branch, 32 noise samples per batch, one per chunk of batch_size / 32 rows (layers.py:57-74); other batch sizes
+take the reference's per-row branch, which is refused (ValueError). Only direct_DQN(noisy_layers=2) is covered.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Mapping, Optional
+
+import torch
+
+from . import _lib as L
+from .actor import _layer_tensors
+from .replay import _view
+
+LAYERS = ("fc1", "fc2", "fc31", "fc41", "fc32", "fc42")
+NOISY = (False, False, True, True, False, False)
+
+
+def _shapes(data_length: int, n_actions: int):
+    return ((512, data_length), (256, 512), (256, 256), (n_actions, 256), (128, 256), (1, 128))
+
+
+class DQNLearner:
+    """TrainDQN for direct_DQN(data_length, noisy_layers=2) with LaProp(centered, betas (0.9, 0.9995))."""
+
+    def __init__(self, params: Mapping[str, torch.Tensor], batch_size: int = 512, gamma: float = 0.998,
+                 lr: float = 4e-4, alive_reward: float = 10., failing_reward: float = -1., backup_period: int = 300,
+                 device: int | str | torch.device = 0, seed: int = 0, data_length: Optional[int] = None,
+                 n_actions: Optional[int] = None):
+        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("DQNLearner runs on a HIP device only (no CPU fallback)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if batch_size % 128 != 0 or not 128 <= batch_size <= 4096:
+            raise ValueError("batch_size must be a multiple of 128 in [128, 4096] (FactorizedNoisy's 32-chunk "
+                             "noise branch; the per-row branch of other sizes is not implemented)")
+        if "fc1.weight" not in params or "fc41.u_w" not in params:
+            raise ValueError("params must be a direct_DQN(noisy_layers=2) state_dict (fc1.weight, ..., fc41.u_w)")
+        self.data_length = int(data_length if data_length is not None else params["fc1.weight"].shape[1])
+        self.n_actions = int(n_actions if n_actions is not None else params["fc41.u_w"].shape[0])
+        self.batch_size = int(batch_size)
+        self.row_len = 2 * self.data_length + 2
+        p = L.QcLearnerParams()
+        p.data_length, p.n_actions, p.batch_size = self.data_length, self.n_actions, self.batch_size
+        p.backup_period, p.gamma, p.lr = int(backup_period), float(gamma), float(lr)
+        p.alive_reward, p.failing_reward, p.seed = float(alive_reward), float(failing_reward), int(seed)
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            torch.cuda.init()
+            L.check_learner(L.lib().qc_learner_create(ctypes.byref(p), self.device.index, ctypes.byref(h)), None)
+        self._h = h
+        self.noise_len = int(L.lib().qc_learner_noise_len(h))
+        self.counter = 0
+        self.last_loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._keep = []
+        self.load_state_dict(params)
+
+    def close(self):
+        if getattr(self, "_h", None):
+            L.lib().qc_learner_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _bind_stream(self):
+        s = torch.cuda.current_stream(self.device).cuda_stream
+        L.check_learner(L.lib().qc_learner_set_stream(self._h, ctypes.c_void_p(s)), self._h)
+
+    def _layer_array(self, params: Mapping[str, torch.Tensor]):
+        layers = (L.QcDqnLayer * 6)()
+        keep = []
+        for i, (name, shape) in enumerate(zip(LAYERS, _shapes(self.data_length, self.n_actions))):
+            if NOISY[i] != (f"{name}.u_w" in params):
+                raise ValueError(f"{name}: the learner covers direct_DQN(noisy_layers=2) only")
+            w, b, g, sw, sb = _layer_tensors(params, name, self.device)
+            if tuple(w.shape) != shape:
+                raise ValueError(f"{name}: weight shape {tuple(w.shape)} != {shape}")
+            keep += [w, b, g, sw, sb]
+            layers[i].weight, layers[i].bias = w.data_ptr(), b.data_ptr()
+            layers[i].weight_norm = g.data_ptr() if g is not None else None
+            layers[i].sigma_w = sw.data_ptr() if sw is not None else None
+            layers[i].sigma_b = sb.data_ptr() if sb is not None else None
+        return layers, keep
+
+    def load_state_dict(self, params: Mapping[str, torch.Tensor]):
+        """Load the six layers from a state_dict (a reference direct_DQN's, or actor.random_direct_dqn's);
+        resets the optimizer state and the target schedule."""
+        layers, keep = self._layer_array(params)
+        with torch.cuda.device(self.device):
+            self._bind_stream()
+            L.check_learner(L.lib().qc_learner_load(self._h, layers), self._h)
+        self._keep = keep   # the copies read them on the current stream
+
+    def _tensors(self, layers) -> dict:
+        out = {}
+        for i, (name, (o, k)) in enumerate(zip(LAYERS, _shapes(self.data_length, self.n_actions))):
+            ly = layers[i]
+            if NOISY[i]:
+                out[f"{name}.u_w"] = _view(ly.weight, o * k, torch.float32, self.device).view(o, k)
+                out[f"{name}.sigma_w"] = _view(ly.sigma_w, o * k, torch.float32, self.device).view(o, k)
+                out[f"{name}.u_b"] = _view(ly.bias, o, torch.float32, self.device)
+                out[f"{name}.sigma_b"] = _view(ly.sigma_b, o, torch.float32, self.device)
+            else:
+                out[f"{name}.weight"] = _view(ly.weight, o * k, torch.float32, self.device).view(o, k)
+                out[f"{name}.bias"] = _view(ly.bias, o, torch.float32, self.device)
+                out[f"{name}.weight_norm"] = _view(ly.weight_norm, 1, torch.float32, self.device).view(())
+        return out
+
+    def state_dict(self, target: bool = False) -> dict:
+        """The online (or target) parameters under the reference's key names, as device copies."""
+        layers = (L.QcDqnLayer * 6)()
+        L.check_learner(L.lib().qc_learner_layers(self._h, 1 if target else 0, layers), self._h)
+        with torch.cuda.device(self.device):
+            return {k: v.clone() for k, v in self._tensors(layers).items()}
+
+    def grads(self) -> dict:
+        """Gradients of the last update under the parameters' key names (weight_norm: dg), as device copies."""
+        layers = (L.QcDqnLayer * 6)()
+        L.check_learner(L.lib().qc_learner_grads(self._h, layers), self._h)
+        with torch.cuda.device(self.device):
+            return {k: v.clone() for k, v in self._tensors(layers).items()}
+
+    def apply(self, grads: Mapping[str, torch.Tensor]):
+        """One LaProp step on injected gradients (tests)."""
+        layers, keep = self._layer_array(grads)
+        with torch.cuda.device(self.device):
+            self._bind_stream()
+            L.check_learner(L.lib().qc_learner_apply(self._h, layers), self._h)
+        self._keep = keep
+
+    def set_lr(self, lr: float):
+        L.check_learner(L.lib().qc_learner_set_lr(self._h, float(lr)), self._h)
+
+    def update(self, transitions: torch.Tensor, is_weights: torch.Tensor, noise: Optional[torch.Tensor] = None,
+               counter: Optional[int] = None) -> torch.Tensor:
+        """One update on transitions [batch_size, 2 data_length + 2] and IS weights [batch_size]. noise: optional
+        [32, noise_len], already f-transformed, the actor's layout per chunk; else Philox (seed, chunk, counter).
+        Returns unweighted_loss [batch_size] (device); the scalar loss stays in `last_loss` (device).
+        Asynchronous: an action outside [0, n_actions) is clamped and raised by the next `stats()`."""
+        if transitions.dim() != 2 or tuple(transitions.shape) != (self.batch_size, self.row_len):
+            raise ValueError(f"transitions must be [{self.batch_size}, {self.row_len}]")
+        if is_weights.numel() != self.batch_size:
+            raise ValueError(f"is_weights must be [{self.batch_size}]")
+        tr = transitions.to(device=self.device, dtype=torch.float32).contiguous()
+        w = is_weights.to(device=self.device, dtype=torch.float32).contiguous()
+        nz = None
+        if noise is not None:
+            if tuple(noise.shape) != (32, self.noise_len):
+                raise ValueError(f"noise must be [32, {self.noise_len}]")
+            nz = noise.to(device=self.device, dtype=torch.float32).contiguous()
+        if counter is None:
+            counter = self.counter
+            self.counter += 1
+        ul = torch.empty(self.batch_size, dtype=torch.float32, device=self.device)
+        vp = ctypes.c_void_p
+        with torch.cuda.device(self.device):
+            self._bind_stream()
+            L.check_learner(L.lib().qc_learner_update(
+                self._h, vp(tr.data_ptr()), vp(w.data_ptr()), vp(nz.data_ptr()) if nz is not None else None,
+                int(counter), vp(ul.data_ptr()), vp(self.last_loss.data_ptr())), self._h)
+        return ul
+
+    def step(self, memory, counter: Optional[int] = None):
+        """TrainDQN.__call__: obtain_sample -> update -> memory.batch_update(tree_idx, unweighted_loss). None
+        while len(memory) < batch_size (RL.py:161)."""
+        smp = memory.obtain_sample(self.batch_size)
+        if smp is None:
+            return None
+        tree_idx, is_weights, transitions = smp
+        ul = self.update(transitions, is_weights, counter=counter)
+        memory.batch_update(tree_idx, ul)
+        return ul
+
+    def push(self, actor):
+        """Load the online fc1, fc2, fc31, fc41 into a DQNActor, device to device (no host copy)."""
+        layers = (L.QcDqnLayer * 6)()
+        L.check_learner(L.lib().qc_learner_layers(self._h, 0, layers), self._h)
+        with torch.cuda.device(self.device):
+            actor._bind_stream()
+            L.check_actor(L.lib().qc_actor_load(actor._h, layers), actor._h)
+
+    def stats(self) -> dict:
+        """Synchronises. Raises QCartError if an update since the last call saw an out-of-range action."""
+        s = L.QcLearnerStats()
+        rc = L.lib().qc_learner_stats(self._h, ctypes.byref(s))
+        L.check_learner(rc, self._h)
+        return {k: getattr(s, k) for k, _ in L.QcLearnerStats._fields_}

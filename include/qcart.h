@@ -430,6 +430,64 @@ int qc_replay_stats(qc_replay* r, qc_replay_stats_t* out);
 /* device pointers of the tree and the row storage (introspection, tests) */
 int qc_replay_buffers(const qc_replay* r, const double** tree, const float** data);
 
+/* ---------------------------------------------------------------------------------------------
+ * Device DQN learner: the reference's TrainDQN.__call__ (inverted harmonic oscillator/RL.py:159-232)
+ * with its LaProp optimizer (optimizer.py; centered, betas (0.9, 0.9995), eps 1e-15, RL.py:145) for the
+ * 'xp' network direct_DQN(data_length, noisy_layers = 2): fc1, fc2, fc31 (noisy), fc41 (noisy) and the mean
+ * head fc32, fc42, fp32 throughout on f32-input MFMA. One update: the target network follows the online
+ * one when backup_counter == 0, then backup_counter = (backup_counter + 1) % backup_period; double-DQN
+ * target a* = argmax Q_online(next), sav = Q(prev)[a] + m(prev) - mean Q(prev), nsv the same of the target
+ * net at a*, y = gamma nsv + (1 - gamma) alive_reward (0 where reward == failing_reward), ul = (sav - y)^2,
+ * loss = mean(ul w); backward through the online pass on prev; one LaProp step. The NoisyNet noise is
+ * FactorizedNoisy's batched branch (layers.py:57-74): the batch is 32 contiguous chunks of B / 32 rows,
+ * one (eps_in, eps_out) pair per chunk and noisy layer, shared by the three forward passes. That branch
+ * needs B % 128 == 0; other batch sizes (the reference's per-row branch) are refused with QC_EINVAL.
+ * Gradients use no atomics: the same inputs give bit-identical parameters. All pointers are device
+ * pointers; every call is asynchronous on the learner's stream except qc_learner_stats. */
+typedef struct qc_learner qc_learner;
+typedef struct qc_learner_params {
+    int32_t data_length, n_actions;
+    int32_t batch_size;            /* multiple of 128, <= 4096 */
+    int32_t backup_period;
+    double gamma, lr, alive_reward, failing_reward;
+    uint64_t seed;                 /* Philox key of the in-kernel noise */
+} qc_learner_params;
+
+typedef struct qc_learner_stats_t {
+    int64_t updates;               /* qc_learner_update calls */
+    int64_t step;                  /* LaProp state['step'] */
+    int64_t nonfinite;             /* updates whose loss was not finite (the reference's NaN assert, RL.py:230) */
+    double l1, l2, lr;             /* exp_avg_lr_1, exp_avg_lr_2, the current lr */
+    int32_t backup_counter;
+    int32_t launches_per_update;   /* kernel launches + copies of the last update */
+} qc_learner_stats_t;
+
+int qc_learner_create(const qc_learner_params* p, int device, qc_learner** out);
+void qc_learner_destroy(qc_learner* l);
+const char* qc_learner_last_error(const qc_learner* l);   /* l may be NULL: last create failure */
+int qc_learner_set_stream(qc_learner* l, void* stream);
+int qc_learner_noise_len(const qc_learner* l);            /* qc_actor_noise_len's layout, per chunk */
+/* layers[6] = fc1, fc2, fc31, fc41, fc32, fc42 (the state_dict tensors, as qc_actor_load); resets the
+ * optimizer state and backup_counter */
+int qc_learner_load(qc_learner* l, const qc_dqn_layer layers[6]);
+/* device pointers to the learner's own natural-layout parameters (target != 0: the target network's):
+ * qc_actor_load takes out[0..3] as they are, so the weight push is device to device */
+int qc_learner_layers(qc_learner* l, int target, qc_dqn_layer out[6]);
+/* transitions [B][2 data_length + 2] (prev, next, action as float, reward), is_weights [B], noise
+ * [32][noise_len] already f-transformed (NULL: Philox keyed by seed, chunk, counter), unweighted_loss [B]
+ * (out, the per-sample losses for qc_replay_update), loss: optional device scalar (out). An action outside
+ * [0, n_actions) is clamped on the device and reported by the next qc_learner_stats. */
+int qc_learner_update(qc_learner* l, const float* transitions, const float* is_weights, const float* noise,
+                      uint64_t counter, float* unweighted_loss, float* loss);
+int qc_learner_set_lr(qc_learner* l, double lr);
+/* synchronises the stream; QC_EINVAL (once, message via qc_learner_last_error) if an update since the last
+ * call saw an out-of-range action, with *out filled either way */
+int qc_learner_stats(qc_learner* l, qc_learner_stats_t* out);
+/* introspection (tests): device pointers to the gradients of the last update, same shapes (the
+ * weight_norm slot holds dg); and one LaProp step on injected gradients */
+int qc_learner_grads(qc_learner* l, qc_dqn_layer out[6]);
+int qc_learner_apply(qc_learner* l, const qc_dqn_layer grads[6]);
+
 /* ---- batched episode loop: the per-control-step bookkeeping of Control.do_episode --------------------------
  * (IHO/main_parallel.py:242-268, IQO/main_parallel.py:190-221; the cartpoles, 'xp' input) for every env after a
  * step call of one control interval, on the device (BatchedEnv reset="deferred"): pending[e] (in) marks the envs

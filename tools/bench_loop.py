@@ -38,7 +38,12 @@ def main():
                          "sync; the default for 'xp', where it applies; immediate for 'measurements')")
     ap.add_argument("--marker", action="store_true",
                     help="wrap the timed steps in a roctx range 'timed' (tools/loop_breakdown.py, rocprofv3 --marker-trace)")
+    ap.add_argument("--learn", type=int, default=0,
+                    help="device learner steps (DQNLearner.step: sample(512) -> update -> batch_update) plus one weight "
+                         "push into the actor per control step; 'xp' input only; 0: none (the default)")
     args = ap.parse_args()
+    if args.learn and args.input != "xp":
+        ap.error("--learn needs --input xp (the learner covers direct_DQN)")
     if args.reset is None:
         args.reset = "deferred" if args.input == "xp" else "immediate"
     B = args.batch
@@ -52,6 +57,10 @@ def main():
     else:
         actor = DQNActor({k: v.cuda() for k, v in random_direct_dqn(seed=1).items()}, max_batch=B, seed=2)
         mem = PrioritizedReplay(args.capacity or 7000 * 18 * 100, 2 * 5 + 2, "random", 0.2, device=0, seed=3)
+    learner = None
+    if args.learn:
+        from deepreinforcementlearningcontrolofquantumcartpoles_amd.learner import DQNLearner
+        learner = DQNLearner(random_direct_dqn(seed=1), batch_size=512, device=0, seed=4)
     obs = env.reset()
     steps_done = 0
     ev = lambda: torch.cuda.Event(enable_timing=True)   # noqa: E731
@@ -88,6 +97,10 @@ def main():
         if smp is not None:
             mem.batch_update(smp[0], torch.rand(512, device="cuda"))
         m[3].record()
+        if learner is not None and it > 0:
+            for _ in range(args.learn):
+                learner.step(mem)
+            learner.push(actor)
         if it >= args.warmup:
             marks.append(m)
     torch.cuda.synchronize()
@@ -100,6 +113,12 @@ def main():
     done_frac = int(n_done) / (B * args.steps)
     K = args.steps
     net = "DQN_measurement" if meas else "direct_DQN"
+    extra = {}
+    if learner is not None:
+        learn_ms = sum(a[3].elapsed_time(b[0]) for a, b in zip(marks[:-1], marks[1:]))
+        extra = {"learn_steps_per_control_step": args.learn,
+                 "learner_ms_per_control_step": learn_ms / max(K - 1, 1),
+                 "learner_nonfinite": learner.stats()["nonfinite"]}
     print(json.dumps({"metric": f"actor loop RL steps/s (BatchedEnv IHO N=512 input={args.input} reset={args.reset} + device {net} actor)",
                       "value": B * K / dt, "unit": "decisions/s", "env_steps_per_s": B * K * ph.control_interval / dt,
                       # physics env-steps actually taken: the immediate mode adds the reset intervals of the envs
@@ -112,7 +131,7 @@ def main():
                       "replay_len": len(mem),
                       "done_fraction_per_control_step": done_frac,
                       "experience_rows_per_s": rows / dt,
-                      "row_len": mem.data_size,
+                      "row_len": mem.data_size, **extra,
                       "data": f"synthetic: |0> resets, random-initialised {net} weights"}), flush=True)
 
 
