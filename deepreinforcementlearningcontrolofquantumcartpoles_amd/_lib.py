@@ -343,36 +343,54 @@ class _Tolerant:
         return getattr(self.lib, name) if hasattr(self.lib, name) else _Tolerant._Sink()
 
 
-def check_actor(rc: int, handle=None) -> int:
-    if rc < 0:
-        msg = lib().qc_actor_last_error(handle)
-        raise QCartError(rc, msg.decode() if msg else "")
-    return rc
+def _checker(prefix: str):
+    """check(rc, handle=None) for the handle family `prefix`: a negative status raises QCartError with
+    <prefix>_last_error(handle) (handle None: the text of a failed <prefix>_create)."""
+    def check(rc: int, handle=None) -> int:
+        if rc < 0:
+            msg = getattr(lib(), prefix + "_last_error")(handle)
+            raise QCartError(rc, msg.decode() if msg else "")
+        return rc
+    return check
 
 
-def check_mactor(rc: int, handle=None) -> int:
-    if rc < 0:
-        msg = lib().qc_mactor_last_error(handle)
-        raise QCartError(rc, msg.decode() if msg else "")
-    return rc
+check = _checker("qc")
+check_actor = _checker("qc_actor")
+check_mactor = _checker("qc_mactor")
+check_learner = _checker("qc_learner")
+check_replay = _checker("qc_replay")
 
 
-def check_learner(rc: int, handle=None) -> int:
-    if rc < 0:
-        msg = lib().qc_learner_last_error(handle)
-        raise QCartError(rc, msg.decode() if msg else "")
-    return rc
+class DeviceHandle:
+    """Owner of one libqcart handle `self._h` on `self.device`, for the handle family `_prefix`
+    (<prefix>_destroy / _set_stream / _last_error)."""
+
+    _prefix = "qc"
+    _h = None
+
+    def _check(self, rc: int) -> int:
+        return _checker(self._prefix)(rc, self._h)
+
+    def close(self):
+        if self._h:
+            getattr(lib(), self._prefix + "_destroy")(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _bind_stream(self):
+        """Later launches of this handle go to torch's current stream of its device."""
+        import torch
+        s = torch.cuda.current_stream(self.device).cuda_stream
+        self._check(getattr(lib(), self._prefix + "_set_stream")(self._h, ctypes.c_void_p(s)))
 
 
-def check_replay(rc: int, handle=None) -> int:
-    if rc < 0:
-        msg = lib().qc_replay_last_error(handle)
-        raise QCartError(rc, msg.decode() if msg else "")
-    return rc
-
-
-def check(rc: int, handle=None) -> int:
-    if rc < 0:
-        msg = lib().qc_last_error(handle)
-        raise QCartError(rc, msg.decode() if msg else "")
-    return rc
+def fill_layer(slot: "QcDqnLayer", tensors) -> None:
+    """Write a layer's (weight, bias, weight_norm, sigma_w, sigma_b) device tensors (None where the layer has
+    none) into a QcDqnLayer; the caller keeps the tensors alive."""
+    for (name, _), t in zip(QcDqnLayer._fields_, tensors):
+        setattr(slot, name, t.data_ptr() if t is not None else None)

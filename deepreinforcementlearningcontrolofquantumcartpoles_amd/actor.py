@@ -39,77 +39,39 @@ def _layer_tensors(params: Mapping[str, torch.Tensor], name: str, dev: torch.dev
     return t("weight"), t("bias"), t("weight_norm").reshape(1), None, None
 
 
-class DQNActor:
-    """Device-side action selection for B envs with a reference direct_DQN's parameters."""
+class _ActorHandle(L.DeviceHandle):
+    """What DQNActor and MeasurementActor share: the handle, and `act` up to the observation's shape."""
 
-    def __init__(self, params: Mapping[str, torch.Tensor], data_length: int = 5, n_actions: int = 21,
-                 max_batch: int = 65536, device: int | str | torch.device = 0, seed: int = 0):
+    def _create(self, p, device, n_actions: int, max_batch: int):
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         if self.device.type != "cuda":
-            raise RuntimeError("DQNActor runs on a HIP device only (no CPU fallback)")
-        self.data_length, self.n_actions, self.max_batch = int(data_length), int(n_actions), int(max_batch)
-        p = L.QcDqnParams()
-        p.data_length, p.n_actions, p.max_batch, p.seed = self.data_length, self.n_actions, self.max_batch, int(seed)
+            raise RuntimeError(f"{type(self).__name__} runs on a HIP device only (no CPU fallback)")
+        self.n_actions, self.max_batch = int(n_actions), int(max_batch)
+        p.n_actions, p.max_batch = self.n_actions, self.max_batch
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            L.check_actor(L.lib().qc_actor_create(ctypes.byref(p), self.device.index or 0, ctypes.byref(h)), None)
+            create = getattr(L.lib(), self._prefix + "_create")
+            self._check(create(ctypes.byref(p), self.device.index or 0, ctypes.byref(h)))   # (no handle yet)
         self._h = h
-        self.noise_len = int(L.lib().qc_actor_noise_len(h))
+        self.noise_len = int(getattr(L.lib(), self._prefix + "_noise_len")(h))
         self.counter = 0
         self._keep = []
-        self.load(params)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            L.lib().qc_actor_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _bind_stream(self):
-        s = torch.cuda.current_stream(self.device).cuda_stream
-        L.check_actor(L.lib().qc_actor_set_stream(self._h, ctypes.c_void_p(s)), self._h)
-
-    def load(self, params: Mapping[str, torch.Tensor]):
-        """(Re)load fc1, fc2, fc31, fc41 from a state_dict (the trainer's periodic push,
-        main_parallel.py:400-405). Noisy / weight-normalised layers are recognised by their keys."""
-        layers = (L.QcDqnLayer * 4)()
-        keep = []
-        for i, name in enumerate(LAYERS):
-            w, b, g, sw, sb = _layer_tensors(params, name, self.device)
-            out_f = HIDDEN[i] if i < 3 else self.n_actions
-            in_f = self.data_length if i == 0 else HIDDEN[i - 1]
-            if tuple(w.shape) != (out_f, in_f):
-                raise ValueError(f"{name}: weight shape {tuple(w.shape)} != {(out_f, in_f)}")
-            keep += [w, b, g, sw, sb]
-            layers[i].weight, layers[i].bias = w.data_ptr(), b.data_ptr()
-            layers[i].weight_norm = g.data_ptr() if g is not None else None
-            layers[i].sigma_w = sw.data_ptr() if sw is not None else None
-            layers[i].sigma_b = sb.data_ptr() if sb is not None else None
+    def _load(self, layers, keep):
         with torch.cuda.device(self.device):
             self._bind_stream()
-            L.check_actor(L.lib().qc_actor_load(self._h, layers), self._h)
+            self._check(getattr(L.lib(), self._prefix + "_load")(self._h, layers))
         self._keep = keep   # the prep kernels read them on the current stream
-
-    @staticmethod
-    def eps_threshold(steps_done: float, start: float = 0.1, end: float = 0.003,
-                      decay: float = 18 * 100 * 300) -> float:
-        """The actor's epsilon schedule (IHO/main_parallel.py:186-189,208-210; decay = n_con*100*300)."""
-        return (start - end) * math.exp(-1.0 * steps_done / decay) + end
 
     def act(self, obs: torch.Tensor, eps: float = 0.0, noisy: bool = True, counter: Optional[int] = None,
             noise: Optional[torch.Tensor] = None, env_offset: int = 0, want_q: bool = False,
             want_random: bool = False):
-        """Actions [B] int32 for obs [B, data_length] (fp32, the network input). noise: optional injected
+        """Actions [B] int32 for obs [B, data_length] (fp32, the network input; MeasurementActor:
+        [B, 2, read_length], the measurement record). noise: optional injected
         NoisyNet noise [B, noise_len] (already f-transformed, layers.py:77-79); else drawn in-kernel
         with Philox (seed, env_offset + e, counter). Returns actions, or (actions, extras) when q / random
         flags are requested."""
-        if obs.dim() != 2 or obs.shape[1] != self.data_length:
-            raise ValueError(f"obs must be [B, {self.data_length}]")
+        self._check_obs(obs)
         B = obs.shape[0]
         if B > self.max_batch:
             raise ValueError(f"B = {B} exceeds max_batch = {self.max_batch}")
@@ -128,14 +90,53 @@ class DQNActor:
         vp = ctypes.c_void_p
         with torch.cuda.device(self.device):
             self._bind_stream()
-            L.check_actor(L.lib().qc_actor_act(
+            self._check(getattr(L.lib(), self._prefix + "_act")(
                 self._h, B, int(env_offset), vp(obs.data_ptr()), 1 if noisy else 0,
                 vp(nz.data_ptr()) if nz is not None else None, float(eps), int(counter),
                 vp(actions.data_ptr()), vp(q.data_ptr()) if q is not None else None,
-                vp(rnd.data_ptr()) if rnd is not None else None), self._h)
+                vp(rnd.data_ptr()) if rnd is not None else None))
         if want_q or want_random:
             return actions, {"q": q, "random": rnd}
         return actions
+
+
+class DQNActor(_ActorHandle):
+    """Device-side action selection for B envs with a reference direct_DQN's parameters."""
+
+    _prefix = "qc_actor"
+
+    def __init__(self, params: Mapping[str, torch.Tensor], data_length: int = 5, n_actions: int = 21,
+                 max_batch: int = 65536, device: int | str | torch.device = 0, seed: int = 0):
+        self.data_length = int(data_length)
+        p = L.QcDqnParams()
+        p.data_length, p.seed = self.data_length, int(seed)
+        self._create(p, device, n_actions, max_batch)
+        self.load(params)
+
+    def load(self, params: Mapping[str, torch.Tensor]):
+        """(Re)load fc1, fc2, fc31, fc41 from a state_dict (the trainer's periodic push,
+        main_parallel.py:400-405). Noisy / weight-normalised layers are recognised by their keys."""
+        layers = (L.QcDqnLayer * 4)()
+        keep = []
+        for i, name in enumerate(LAYERS):
+            t = _layer_tensors(params, name, self.device)
+            out_f = HIDDEN[i] if i < 3 else self.n_actions
+            in_f = self.data_length if i == 0 else HIDDEN[i - 1]
+            if tuple(t[0].shape) != (out_f, in_f):
+                raise ValueError(f"{name}: weight shape {tuple(t[0].shape)} != {(out_f, in_f)}")
+            keep += t
+            L.fill_layer(layers[i], t)
+        self._load(layers, keep)
+
+    @staticmethod
+    def eps_threshold(steps_done: float, start: float = 0.1, end: float = 0.003,
+                      decay: float = 18 * 100 * 300) -> float:
+        """The actor's epsilon schedule (IHO/main_parallel.py:186-189,208-210; decay = n_con*100*300)."""
+        return (start - end) * math.exp(-1.0 * steps_done / decay) + end
+
+    def _check_obs(self, obs):
+        if obs.dim() != 2 or obs.shape[1] != self.data_length:
+            raise ValueError(f"obs must be [B, {self.data_length}]")
 
 
 def random_direct_dqn(data_length: int = 5, n_actions: int = 21, noisy_layers: int = 2, seed: int = 0,
@@ -185,43 +186,20 @@ def measurement_flat_len(read_length: int) -> int:
     return 64 * n
 
 
-class MeasurementActor:
+class MeasurementActor(_ActorHandle):
     """Device-side action selection for B envs with a reference DQN_measurement's parameters (the
     'measurements' input, IHO/RL.py:29-78): obs = MeasurementRecord.hist [B, 2, read_length]."""
 
+    _prefix = "qc_mactor"
+
     def __init__(self, params: Mapping[str, torch.Tensor], read_length: int = 5760, n_actions: int = 21,
                  max_batch: int = 65536, device: int | str | torch.device = 0, seed: int = 0, chunk: int = 0):
-        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("MeasurementActor runs on a HIP device only (no CPU fallback)")
-        self.read_length, self.n_actions, self.max_batch = int(read_length), int(n_actions), int(max_batch)
+        self.read_length = int(read_length)
         p = L.QcMdqnParams()
-        p.read_length, p.n_actions, p.max_batch, p.seed, p.chunk = (self.read_length, self.n_actions,
-                                                                     self.max_batch, int(seed), int(chunk))
-        h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            L.check_mactor(L.lib().qc_mactor_create(ctypes.byref(p), self.device.index or 0, ctypes.byref(h)), None)
-        self._h = h
-        self.noise_len = int(L.lib().qc_mactor_noise_len(h))
-        self.flat_len = int(L.lib().qc_mactor_flat_len(h))
-        self.counter = 0
-        self._keep = []
+        p.read_length, p.seed, p.chunk = self.read_length, int(seed), int(chunk)
+        self._create(p, device, n_actions, max_batch)
+        self.flat_len = int(L.lib().qc_mactor_flat_len(self._h))
         self.load(params)
-
-    def close(self):
-        if getattr(self, "_h", None):
-            L.lib().qc_mactor_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _bind_stream(self):
-        s = torch.cuda.current_stream(self.device).cuda_stream
-        L.check_mactor(L.lib().qc_mactor_set_stream(self._h, ctypes.c_void_p(s)), self._h)
 
     def load(self, params: Mapping[str, torch.Tensor]):
         layers = (L.QcDqnLayer * 6)()
@@ -232,53 +210,18 @@ class MeasurementActor:
                 w = params[f"{name}.weight"].detach().to(device=self.device, dtype=torch.float32)
                 w = w.reshape(w.shape[0], -1).contiguous()
                 b = params[f"{name}.bias"].detach().to(device=self.device, dtype=torch.float32).contiguous()
-                g = sw = sb = None
+                t = (w, b, None, None, None)
             else:
-                w, b, g, sw, sb = _layer_tensors(params, name, self.device)
-            if tuple(w.shape) != shapes[j]:
-                raise ValueError(f"{name}: weight shape {tuple(w.shape)} != {shapes[j]}")
-            keep += [w, b, g, sw, sb]
-            layers[j].weight, layers[j].bias = w.data_ptr(), b.data_ptr()
-            layers[j].weight_norm = g.data_ptr() if g is not None else None
-            layers[j].sigma_w = sw.data_ptr() if sw is not None else None
-            layers[j].sigma_b = sb.data_ptr() if sb is not None else None
-        with torch.cuda.device(self.device):
-            self._bind_stream()
-            L.check_mactor(L.lib().qc_mactor_load(self._h, layers), self._h)
-        self._keep = keep
+                t = _layer_tensors(params, name, self.device)
+            if tuple(t[0].shape) != shapes[j]:
+                raise ValueError(f"{name}: weight shape {tuple(t[0].shape)} != {shapes[j]}")
+            keep += t
+            L.fill_layer(layers[j], t)
+        self._load(layers, keep)
 
-    def act(self, obs: torch.Tensor, eps: float = 0.0, noisy: bool = True, counter: Optional[int] = None,
-            noise: Optional[torch.Tensor] = None, env_offset: int = 0, want_q: bool = False,
-            want_random: bool = False):
-        """As DQNActor.act for obs [B, 2, read_length] (the measurement record)."""
+    def _check_obs(self, obs):
         if obs.dim() != 3 or obs.shape[1] != 2 or obs.shape[2] != self.read_length:
             raise ValueError(f"obs must be [B, 2, {self.read_length}]")
-        B = obs.shape[0]
-        if B > self.max_batch:
-            raise ValueError(f"B = {B} exceeds max_batch = {self.max_batch}")
-        obs = obs.to(device=self.device, dtype=torch.float32).contiguous()
-        if counter is None:
-            counter = self.counter
-            self.counter += 1
-        nz = None
-        if noise is not None:
-            if tuple(noise.shape) != (B, self.noise_len):
-                raise ValueError(f"noise must be [B, {self.noise_len}]")
-            nz = noise.to(device=self.device, dtype=torch.float32).contiguous()
-        actions = torch.empty(B, dtype=torch.int32, device=self.device)
-        q = torch.empty((B, self.n_actions), dtype=torch.float32, device=self.device) if want_q else None
-        rnd = torch.empty(B, dtype=torch.int32, device=self.device) if want_random else None
-        vp = ctypes.c_void_p
-        with torch.cuda.device(self.device):
-            self._bind_stream()
-            L.check_mactor(L.lib().qc_mactor_act(
-                self._h, B, int(env_offset), vp(obs.data_ptr()), 1 if noisy else 0,
-                vp(nz.data_ptr()) if nz is not None else None, float(eps), int(counter),
-                vp(actions.data_ptr()), vp(q.data_ptr()) if q is not None else None,
-                vp(rnd.data_ptr()) if rnd is not None else None), self._h)
-        if want_q or want_random:
-            return actions, {"q": q, "random": rnd}
-        return actions
 
 
 def random_dqn_measurement(read_length: int = 5760, n_actions: int = 21, seed: int = 0,

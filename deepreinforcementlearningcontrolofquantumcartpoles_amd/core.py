@@ -43,7 +43,7 @@ def make_params(physics: Physics, batch: int, seed: int = 42, env_offset: int = 
     return p
 
 
-class Stepper:
+class Stepper(L.DeviceHandle):
     """B environments of one physical system on one device (one handle, one HIP stream)."""
 
     def __init__(self, physics: Physics, batch: int, device: int | str | torch.device = 0, seed: int = 42,
@@ -66,22 +66,6 @@ class Stepper:
         self.N = L.lib().qc_dim(h)
         self.n_obs = L.lib().qc_n_obs(h)
         self.n_slots = physics.n_actions   # grows with add_force
-
-    # ------------------------------------------------------------------ lifecycle
-    def close(self):
-        if getattr(self, "_h", None):
-            L.lib().qc_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _bind_stream(self):
-        s = torch.cuda.current_stream(self.device).cuda_stream
-        L.check(L.lib().qc_set_stream(self._h, ctypes.c_void_p(s)), self._h)
 
     @property
     def state_dtype(self) -> torch.dtype:

@@ -5,31 +5,21 @@
 // layers.py:97-103 (Linear_weight_normalize), main_parallel.py:208-219 (epsilon-greedy in the actor) and
 // :414-440 (the inference process: argmax of the action values).
 //
-// Design (MI355X): one workgroup = 32 envs x 4 waves. Every layer is Y[o][env] = W[o][k] X[k][env] on
-// the f32-input MFMA v_mfma_f32_32x32x2_f32 (exact f32 accumulation): A = the layer's weights, stored
-// once per load in fragment order (one coalesced 256-B read per MFMA), B = the activations in LDS as
-// [feature][32 envs] (one conflict-free ds_read_b32 per MFMA), D = a 32-feature x 32-env tile whose
-// rows land in the 16 accumulator registers. The epilogue adds bias / noise, applies ReLU and writes
-// the next layer's input back to LDS; activations never leave the CU. A factorised noisy layer is two
-// GEMMs per tile: u_w X and sigma_w (eps_in o X), combined as
-//   y = u_w x + u_b + eps_out o (sigma_w (eps_in o x) + sigma_b)   (== (u_w + sigma_w o eps_out eps_in^T) x + ...)
+// The network itself (workgroup shape, fragment GEMMs, the noisy-layer scheme, the noise layout) is
+// qcart_dqn.hpp's; this file holds the actor's epilogues, the measurement network's convolutions and the handles.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <mutex>
 #include <string>
 
 #include "../../include/qcart.h"
-#include "qcart_kernels.hpp"
-#include "qcart_mfma.hpp"
+#include "qcart_dqn.hpp"
+#include "qcart_host.hpp"
 
 namespace qcart {
 namespace actor {
 
-using namespace qcart::mfma;          // kE, f32x16, tiles / ksteps, gemm_tile, drow (qcart_mfma.hpp)
-constexpr int kH1 = 512, kH2 = 256, kH3 = 256;
-constexpr int kMaxIn = 512;            // data_length limit (LDS: [in][32] fp32 within 64 KiB)
-constexpr int kThreads = 256;
+using namespace qcart::dqn;
 
 struct Layer {
     const float* u;      // fragments of the (effective) weight
@@ -65,7 +55,7 @@ __global__ __launch_bounds__(kThreads) void k_actor_act(const ActArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* RA = lds;                      // H1 [512][32]; later H3 [256][32] + H3e [256][32]
     float* RB = lds + kH1 * kE;           // X0 [in_pad][32]; later H2 [256][32] + H2e [256][32]
-    float* RC = lds + 2 * kH1 * kE;       // fc41 sigma partial [32 rows][64 lanes... as D regs]
+    float* RC = lds + 2 * kH1 * kE;       // fc41 sigma partial
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t e0 = (int64_t)blockIdx.x * kE;
     const int env = lane & 31;
@@ -82,93 +72,59 @@ __global__ __launch_bounds__(kThreads) void k_actor_act(const ActArgs a) {
             const bool ok = e0 + e < a.B;
             const float h = ok ? a.h_in[(int64_t)k * a.h_ld + e0 + e] : 0.f;
             H2[i] = h;
-            if (n31) H2e[i] = ok ? h * noise_at(a, k, e0 + e) : 0.f;
+            if (n31) H2e[i] = ok ? h * noise_at(a, kEpsIn31 + k, e0 + e) : 0.f;
         }
         __syncthreads();
-        goto fc31;
-    }
-    // ---- input: the fp32 network input (IHO/main_parallel.py:131,241) -> X0[k][env]
-    for (int i = tid; i < a.in_pad * kE; i += kThreads) {
-        const int k = i / kE, e = i % kE;
-        RB[i] = (k < a.in_len && e0 + e < a.B) ? a.obs[(e0 + e) * a.in_len + k] : 0.f;
-    }
-    __syncthreads();
-
-    // ---- fc1: 512 outputs = 16 tiles, 4 per wave; ReLU
-    for (int t = wave; t < tiles(kH1); t += 4) {
-        f32x16 acc = {};
-        gemm_tile(acc, a.L[0].u + (size_t)t * ksteps(a.in_pad) * 64, RB, ksteps(a.in_pad), lane);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int o = t * 32 + drow(r, lane);
-            RA[o * kE + env] = fmaxf(acc[r] + a.L[0].ub[o], 0.f);
+    } else {
+        // ---- input: the fp32 network input (IHO/main_parallel.py:131,241) -> X0[k][env]
+        for (int i = tid; i < a.in_pad * kE; i += kThreads) {
+            const int k = i / kE, e = i % kE;
+            RB[i] = (k < a.in_len && e0 + e < a.B) ? a.obs[(e0 + e) * a.in_len + k] : 0.f;
         }
-    }
-    __syncthreads();
-
-    // ---- fc2: 256 outputs = 8 tiles, 2 per wave; ReLU; also eps_in(fc31) o H2 for the noisy GEMM
-    for (int t = wave; t < tiles(kH2); t += 4) {
-        f32x16 acc = {};
-        gemm_tile(acc, a.L[1].u + (size_t)t * ksteps(kH1) * 64, RA, ksteps(kH1), lane);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int o = t * 32 + drow(r, lane);
-            const float h = fmaxf(acc[r] + a.L[1].ub[o], 0.f);
+        __syncthreads();
+        // ---- fc1: ReLU
+        dense4(a.L[0].u, nullptr, RB, nullptr, kH1, a.in_pad, lane, wave, [&](int o, float y, float) {
+            RA[o * kE + env] = fmaxf(y + a.L[0].ub[o], 0.f);
+        });
+        __syncthreads();
+        // ---- fc2: ReLU; also eps_in(fc31) o H2 for the noisy GEMM
+        dense4(a.L[1].u, nullptr, RA, nullptr, kH2, kH1, lane, wave, [&](int o, float y, float) {
+            const float h = fmaxf(y + a.L[1].ub[o], 0.f);
             H2[o * kE + env] = h;
-            if (n31) H2e[o * kE + env] = env_ok ? h * noise_at(a, o, eg) : 0.f;
-        }
+            if (n31) H2e[o * kE + env] = env_ok ? h * noise_at(a, kEpsIn31 + o, eg) : 0.f;
+        });
+        __syncthreads();
     }
-    __syncthreads();
 
-    // ---- fc31 (noisy or weight-normalised): 8 tiles, 2 per wave; ReLU; eps_in(fc41) o H3
-fc31:
+    // ---- fc31 (noisy or weight-normalised): ReLU; eps_in(fc41) o H3
     float* H3 = RA;
     float* H3e = RA + kH3 * kE;
     const bool n41 = a.noisy && a.L[3].s != nullptr;
-    for (int t = wave; t < tiles(kH3); t += 4) {
-        f32x16 acc = {}, accs = {};
-        gemm_tile(acc, a.L[2].u + (size_t)t * ksteps(kH2) * 64, H2, ksteps(kH2), lane);
-        if (n31) gemm_tile(accs, a.L[2].s + (size_t)t * ksteps(kH2) * 64, H2e, ksteps(kH2), lane);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int o = t * 32 + drow(r, lane);
-            float y = acc[r] + a.L[2].ub[o];
-            if (n31) y += env_ok ? noise_at(a, kH2 + o, eg) * (accs[r] + a.L[2].sb[o]) : 0.f;
-            const float h = fmaxf(y, 0.f);
-            H3[o * kE + env] = h;
-            if (n41) H3e[o * kE + env] = env_ok ? h * noise_at(a, 2 * kH2 + o, eg) : 0.f;
-        }
-    }
+    dense4(a.L[2].u, n31 ? a.L[2].s : nullptr, H2, H2e, kH3, kH2, lane, wave, [&](int o, float yu, float ys) {
+        float y = yu + a.L[2].ub[o];
+        if (n31) y += env_ok ? noise_at(a, kEpsOut31 + o, eg) * (ys + a.L[2].sb[o]) : 0.f;
+        const float h = fmaxf(y, 0.f);
+        H3[o * kE + env] = h;
+        if (n41) H3e[o * kE + env] = env_ok ? h * noise_at(a, kEpsIn41 + o, eg) : 0.f;
+    });
     __syncthreads();
 
-    // ---- fc41: one 32-row tile; wave 0: u_w H3, wave 1: sigma_w (eps_in o H3) -> LDS partial
-    if (wave == 1 && n41) {
-        f32x16 accs = {};
-        gemm_tile(accs, a.L[3].s, H3e, ksteps(kH3), lane);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) RC[r * 64 + lane] = accs[r];
-    }
-    f32x16 acc = {};
-    if (wave == 0) gemm_tile(acc, a.L[3].u, H3, ksteps(kH3), lane);
-    __syncthreads();
-    if (wave != 0) return;
-
-    // ---- action values, argmax (lowest index among equal maxima), epsilon-greedy
+    // ---- fc41 -> action values, argmax (lowest index among equal maxima)
     float best = -INFINITY;
     int besti = 0x7fffffff;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int o = drow(r, lane);
-        if (o < a.n_act) {
-            float q = acc[r] + a.L[3].ub[o];
-            if (n41) q += env_ok ? noise_at(a, 2 * kH2 + kH3 + o, eg) * (RC[r * 64 + lane] + a.L[3].sb[o]) : 0.f;
-            if (a.q_out && env_ok) a.q_out[eg * a.n_act + o] = q;
-            if (q > best || (q == best && o < besti)) {
-                best = q;
-                besti = o;
-            }
-        }
-    }
+    const bool w0 = fc41(a.L[3].u, n41 ? a.L[3].s : nullptr, H3, H3e, RC, a.n_act, lane, wave,
+                         [&](int o, float yu, float ys) {
+                             float q = yu + a.L[3].ub[o];
+                             if (n41) q += env_ok ? noise_at(a, kEpsOut41 + o, eg) * (ys + a.L[3].sb[o]) : 0.f;
+                             if (a.q_out && env_ok) a.q_out[eg * a.n_act + o] = q;
+                             if (q > best || (q == best && o < besti)) {
+                                 best = q;
+                                 besti = o;
+                             }
+                         },
+                         [] {});
+    if (!w0) return;
+    // ---- epsilon-greedy
     const float ob = __shfl_xor(best, 32, 64);
     const int oi = __shfl_xor(besti, 32, 64);
     if (ob > best || (ob == best && oi < besti)) besti = oi;
@@ -196,16 +152,9 @@ __global__ __launch_bounds__(256) void k_actor_noise(float* out, int64_t ld, int
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const int p = blockIdx.y;
     if (e >= B) return;
-    // Box-Muller in fp32 (hardware log / sin / cos): the network noise is fp32 and has no oracle stream
-    uint32_t c[4] = {(uint32_t)counter, (uint32_t)(counter >> 32), (uint32_t)(env_offset + e), 0x100u + (uint32_t)p};
-    philox10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    const float u1 = ((float)(c[0] >> 8) + 0.5f) * 0x1.0p-24f, u2 = (float)(c[1] >> 8) * 0x1.0p-24f;
-    const float rad = sqrtf(-2.f * __logf(u1));
-    float sn, cs;
-    __sincosf(6.283185307f * u2, &sn, &cs);
-    const float f0 = rad * cs, f1 = rad * sn;
-    out[(int64_t)(2 * p) * ld + e] = copysignf(sqrtf(fabsf(f0)), f0);
-    if (2 * p + 1 < noise_len) out[(int64_t)(2 * p + 1) * ld + e] = copysignf(sqrtf(fabsf(f1)), f1);
+    const float2 f = noise_pair(seed, counter, (uint32_t)(env_offset + e), p);
+    out[(int64_t)(2 * p) * ld + e] = f.x;
+    if (2 * p + 1 < noise_len) out[(int64_t)(2 * p + 1) * ld + e] = f.y;
 }
 
 // injected noise [B][noise_len] -> feature-major [noise_len][ld]
@@ -228,13 +177,8 @@ __global__ __launch_bounds__(1024) void k_actor_prep(const float* W, const float
     if (g) {
         for (int i = threadIdx.x; i < O * K; i += 1024) ss += (double)W[i] * (double)W[i];
     }
-    part[threadIdx.x] = ss;
-    __syncthreads();
-    for (int w = 512; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
-        __syncthreads();
-    }
-    const float sc = g ? (float)((double)g[0] / sqrt(part[0])) : 1.f;
+    ss = block_sum(ss, part);
+    const float sc = g ? wn_scale(g[0], ss) : 1.f;
     const int T = tiles(O), S = ksteps(Kpad);
     for (int i = threadIdx.x; i < T * S * 64; i += 1024) {
         int o, k;
@@ -511,42 +455,84 @@ __global__ __launch_bounds__(256) void k_mfc(const float* __restrict__ X, int64_
 }  // namespace qcart
 
 using namespace qcart::actor;
+using namespace qcart::host;
 
-struct qc_actor {
-    qc_dqn_params p{};
+// what both actor handles hold, and act_tail works on
+struct ActorCore {
     int device = 0;
     hipStream_t stream = nullptr;
-    int in_pad = 0, noise_len = 0;
-    bool loaded = false;
-    bool has_s[4] = {false, false, false, false};
     std::string err;
+    bool loaded = false;
+    int n_act = 0, noise_len = 0;
+    int64_t max_batch = 0;       // also the noise buffer's leading dimension
+    uint64_t seed = 0;
     float* d_w = nullptr;        // all fragments + padded biases
-    size_t off_u[4]{}, off_s[4]{}, off_ub[4]{}, off_sb[4]{};
-    size_t w_floats = 0;
     float* d_noise = nullptr;    // [noise_len][max_batch]
+    Layer L[4]{};                // k_actor_act's layers (s / sb null where loaded without sigma)
+};
+
+struct qc_actor : ActorCore {
+    qc_dqn_params p{};
+    int in_pad = 0;
+    size_t off_u[4]{}, off_s[4]{}, off_ub[4]{}, off_sb[4]{};
 };
 
 namespace {
-std::mutex g_actor_mu;
-std::string g_actor_err;
+CreateError g_actor_err, g_mactor_err;
 
-struct Dev {
-    int prev = -1;
-    explicit Dev(int d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != d) (void)hipSetDevice(d);
-    }
-    ~Dev() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
+constexpr LayerRule kActorRules[] = {
+    {0b0011, states_where([](bool wn, bool sw, bool) { return !wn || sw; }),
+     "fc1 / fc2 are Linear_weight_normalize layers (weight_norm required, no sigma)"},
+    {0b1111, kSigmaApart, kSigmaApartText},
+    {0b1111, states_where([](bool wn, bool sw, bool) { return sw && wn; }), "a noisy layer has no weight_norm"},
+    {0b1111, states_where([](bool wn, bool sw, bool) { return !sw && !wn; }), "a deterministic layer needs weight_norm"},
+};
+constexpr LayerRule kMactorRules[] = {
+    {0b001111, states_where([](bool wn, bool sw, bool) { return sw || wn; }),
+     "conv1..3 and fc1 are plain Conv1d / Linear layers (no weight_norm, no sigma)"},
+    {0b111111, kSigmaApart, kSigmaApartText},
+    {0b110000, states_where([](bool wn, bool sw, bool) { return !sw && !wn; }),
+     "fc21 / fc31: FactorizedNoisy or Linear_weight_normalize"},
 };
 
-int hip_fail(qc_actor* a, hipError_t e, const char* what) {
-    a->err = std::string(what) + ": " + hipGetErrorString(e);
-    return QC_EHIP;
+bool enable_act_lds() {
+    return hipFuncSetAttribute((const void*)k_actor_act, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)kActLdsBytes) == hipSuccess;
 }
 
-constexpr int kLayerO[4] = {kH1, kH2, kH3, 0};
+// the end of an act call: the noise (injected and transposed, or drawn), then k_actor_act; k holds the input side
+int act_tail(ActorCore* a, ActArgs& k, const char* what, int64_t B, int64_t env_offset, int32_t noisy,
+             const float* noise, double eps, uint64_t counter, int32_t* actions, float* q_out, int32_t* random_out) {
+    const int64_t ld = a->max_batch;
+    const bool need_noise = noisy && (a->L[2].s || a->L[3].s);
+    if (need_noise) {
+        if (noise) {
+            const int64_t n = B * a->noise_len;
+            hipLaunchKernelGGL(k_actor_transpose, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, a->stream, noise,
+                               a->d_noise, ld, B, a->noise_len);
+        } else {
+            hipLaunchKernelGGL(k_actor_noise, dim3((unsigned)((B + 255) / 256), (unsigned)((a->noise_len + 1) / 2)),
+                               dim3(256), 0, a->stream, a->d_noise, ld, B, a->noise_len, env_offset, a->seed, counter);
+        }
+    }
+    for (int l = 0; l < 4; ++l) k.L[l] = a->L[l];
+    k.n_act = a->n_act;
+    k.B = B;
+    k.env_offset = env_offset;
+    k.noisy = need_noise ? 1 : 0;
+    k.noise = a->d_noise;
+    k.noise_ld = ld;
+    k.eps = (float)eps;
+    k.seed = a->seed;
+    k.counter = counter;
+    k.actions = actions;
+    k.q_out = q_out;
+    k.random_out = random_out;
+    hipLaunchKernelGGL(k_actor_act, dim3((unsigned)((B + kE - 1) / kE)), dim3(kThreads), kActLdsBytes, a->stream, k);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return hip_fail(a->err, e, what);
+    return QC_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -554,53 +540,36 @@ extern "C" {
 int qc_actor_create(const qc_dqn_params* p, int device, qc_actor** out) {
     if (!out || !p) return QC_EINVAL;
     *out = nullptr;
-    auto fail = [](const char* m, int rc) {
-        std::lock_guard<std::mutex> lk(g_actor_mu);
-        g_actor_err = m;
-        return rc;
-    };
-    if (p->data_length < 1 || p->data_length > kMaxIn) return fail("data_length must be in [1, 512]", QC_EINVAL);
-    if (p->n_actions < 1 || p->n_actions > 32) return fail("n_actions must be in [1, 32]", QC_EINVAL);
-    if (p->max_batch < 1) return fail("max_batch must be >= 1", QC_EINVAL);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail("no HIP device available (the actor has no CPU fallback)", QC_EHIP);
-    if (device < 0 || device >= ndev) return fail("device index out of range", QC_EINVAL);
+    if (const char* m = bad_net_size(p->data_length, p->n_actions)) return g_actor_err.fail(m, QC_EINVAL);
+    if (p->max_batch < 1) return g_actor_err.fail("max_batch must be >= 1", QC_EINVAL);
+    if (const int rc = check_device(device, g_actor_err, "the actor")) return rc;
     qc_actor* a = new qc_actor();
     a->p = *p;
     a->device = device;
-    a->in_pad = (p->data_length + 1) & ~1;
-    a->noise_len = 2 * kH2 + kH3 + p->n_actions;
+    a->n_act = p->n_actions;
+    a->max_batch = p->max_batch;
+    a->seed = p->seed;
+    a->in_pad = in_pad(p->data_length);
+    a->noise_len = noise_len(p->n_actions);
     const int K[4] = {a->in_pad, kH1, kH2, kH3};
     const int O[4] = {kH1, kH2, kH3, p->n_actions};
-    size_t off = 0;
-    for (int l = 0; l < 4; ++l) {
-        const size_t fr = (size_t)tiles(O[l]) * ksteps(K[l]) * 64, bp = (size_t)tiles(O[l]) * 32;
-        a->off_u[l] = off; off += fr;
-        a->off_s[l] = off; off += fr;
-        a->off_ub[l] = off; off += bp;
-        a->off_sb[l] = off; off += bp;
-    }
-    a->w_floats = off;
+    // fc31 / fc41 may be loaded either way; fc1 / fc2 never use their sigma regions, but without them fc2's
+    // fragments start off a 4 KiB boundary and k_actor_act measures 1.3 % slower (65 536 envs)
+    const bool noisy[4] = {true, true, true, true};
+    const size_t floats = frag_layout(4, O, K, noisy, a->off_u, a->off_s, a->off_ub, a->off_sb);
     Dev g(device);
-    hipError_t e = hipMalloc(&a->d_w, off * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(a->d_w, 0, off * sizeof(float));
+    hipError_t e = hipMalloc(&a->d_w, floats * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(a->d_w, 0, floats * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(&a->d_noise, (size_t)a->noise_len * (size_t)p->max_batch * sizeof(float));
-    if (e != hipSuccess) {
+    const bool lds_ok = e == hipSuccess && enable_act_lds();
+    if (!lds_ok) {
         if (a->d_w) (void)hipFree(a->d_w);
         if (a->d_noise) (void)hipFree(a->d_noise);
         delete a;
-        return fail("device allocation failed", QC_ENOMEM);
-    }
-    if (hipFuncSetAttribute((const void*)k_actor_act, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (2 * kH1 * kE + 16 * 64) * (int)sizeof(float)) != hipSuccess) {
-        (void)hipFree(a->d_w);
-        (void)hipFree(a->d_noise);
-        delete a;
-        return fail("cannot enable 140 KiB of LDS for the actor kernel", QC_EHIP);
+        return e != hipSuccess ? g_actor_err.fail("device allocation failed", QC_ENOMEM)
+                               : g_actor_err.fail("cannot enable 140 KiB of LDS for the actor kernel", QC_EHIP);
     }
     *out = a;
-    (void)kLayerO;
     return QC_OK;
 }
 
@@ -615,11 +584,7 @@ void qc_actor_destroy(qc_actor* a) {
     delete a;
 }
 
-const char* qc_actor_last_error(const qc_actor* a) {
-    if (a) return a->err.c_str();
-    std::lock_guard<std::mutex> lk(g_actor_mu);
-    return g_actor_err.c_str();
-}
+const char* qc_actor_last_error(const qc_actor* a) { return a ? a->err.c_str() : g_actor_err.text(); }
 
 int qc_actor_set_stream(qc_actor* a, void* stream) {
     if (!a) return QC_EINVAL;
@@ -631,33 +596,24 @@ int qc_actor_noise_len(const qc_actor* a) { return a ? a->noise_len : QC_EINVAL;
 
 int qc_actor_load(qc_actor* a, const qc_dqn_layer layers[4]) {
     if (!a || !layers) return QC_EINVAL;
+    if (const int rc = validate_layers(layers, 4, kActorRules, 4, a->err)) return rc;
     const int K[4] = {a->p.data_length, kH1, kH2, kH3};
     const int Kp[4] = {a->in_pad, kH1, kH2, kH3};
     const int O[4] = {kH1, kH2, kH3, a->p.n_actions};
-    for (int l = 0; l < 4; ++l) {
-        const qc_dqn_layer& L = layers[l];
-        if (!L.weight || !L.bias) { a->err = "layer " + std::to_string(l) + ": weight and bias are required"; return QC_EINVAL; }
-        if (l < 2 && (!L.weight_norm || L.sigma_w)) {
-            a->err = "fc1 / fc2 are Linear_weight_normalize layers (weight_norm required, no sigma)";
-            return QC_EINVAL;
-        }
-        if ((L.sigma_w == nullptr) != (L.sigma_b == nullptr)) { a->err = "sigma_w and sigma_b go together"; return QC_EINVAL; }
-        if (L.sigma_w && L.weight_norm) { a->err = "a noisy layer has no weight_norm"; return QC_EINVAL; }
-        if (!L.sigma_w && !L.weight_norm) { a->err = "a deterministic layer needs weight_norm"; return QC_EINVAL; }
-    }
     Dev g(a->device);
     float* w = a->d_w;
     for (int l = 0; l < 4; ++l) {
         const qc_dqn_layer& L = layers[l];
         hipLaunchKernelGGL(k_actor_prep, dim3(1), dim3(1024), 0, a->stream, L.weight, L.weight_norm, O[l], K[l], Kp[l],
                            w + a->off_u[l], L.bias, w + a->off_ub[l], 0);
-        a->has_s[l] = L.sigma_w != nullptr;
         if (L.sigma_w)
             hipLaunchKernelGGL(k_actor_prep, dim3(1), dim3(1024), 0, a->stream, L.sigma_w, (const float*)nullptr, O[l],
                                K[l], Kp[l], w + a->off_s[l], L.sigma_b, w + a->off_sb[l], 0);
+        a->L[l] = Layer{w + a->off_u[l], L.sigma_w ? w + a->off_s[l] : nullptr, w + a->off_ub[l],
+                        L.sigma_w ? w + a->off_sb[l] : nullptr};
     }
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(a, e, "actor weight preparation");
+    if (e != hipSuccess) return hip_fail(a->err, e, "actor weight preparation");
     a->loaded = true;
     return QC_OK;
 }
@@ -670,64 +626,24 @@ int qc_actor_act(qc_actor* a, int64_t B, int64_t env_offset, const float* obs, i
     if (B == 0) return QC_OK;
     if (!obs || !actions) { a->err = "obs and actions are required"; return QC_EINVAL; }
     Dev g(a->device);
-    const bool need_noise = noisy && (a->has_s[2] || a->has_s[3]);
-    if (need_noise) {
-        if (noise) {
-            const int64_t n = B * a->noise_len;
-            hipLaunchKernelGGL(k_actor_transpose, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, a->stream, noise,
-                               a->d_noise, a->p.max_batch, B, a->noise_len);
-        } else {
-            hipLaunchKernelGGL(k_actor_noise, dim3((unsigned)((B + 255) / 256), (unsigned)((a->noise_len + 1) / 2)),
-                               dim3(256), 0, a->stream, a->d_noise, a->p.max_batch, B, a->noise_len, env_offset,
-                               a->p.seed, counter);
-        }
-    }
     ActArgs k{};
-    for (int l = 0; l < 4; ++l) {
-        k.L[l].u = a->d_w + a->off_u[l];
-        k.L[l].ub = a->d_w + a->off_ub[l];
-        k.L[l].s = a->has_s[l] ? a->d_w + a->off_s[l] : nullptr;
-        k.L[l].sb = a->has_s[l] ? a->d_w + a->off_sb[l] : nullptr;
-    }
     k.in_len = a->p.data_length;
     k.in_pad = a->in_pad;
-    k.n_act = a->p.n_actions;
-    k.B = B;
-    k.env_offset = env_offset;
     k.obs = obs;
-    k.noisy = need_noise ? 1 : 0;
-    k.noise = a->d_noise;
-    k.noise_ld = a->p.max_batch;
-    k.eps = (float)eps;
-    k.seed = a->p.seed;
-    k.counter = counter;
-    k.actions = actions;
-    k.q_out = q_out;
-    k.random_out = random_out;
-    hipLaunchKernelGGL(k_actor_act, dim3((unsigned)((B + kE - 1) / kE)), dim3(kThreads),
-                       (2 * kH1 * kE + 16 * 64) * sizeof(float), a->stream, k);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(a, e, "actor launch");
-    return QC_OK;
+    return act_tail(a, k, "actor launch", B, env_offset, noisy, noise, eps, counter, actions, q_out, random_out);
 }
 
 }  // extern "C"
 
 // ---- the measurement-input actor (DQN_measurement, IHO/RL.py:29-78) --------------------------------
-struct qc_mactor {
+struct qc_mactor : ActorCore {
     qc_mdqn_params p{};
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
-    int T1 = 0, T2 = 0, T3 = 0, flat = 0, chunk = 0, noise_len = 0;
-    bool loaded = false, has_s21 = false, has_s31 = false;
-    float* d_w = nullptr;
+    int T1 = 0, T2 = 0, T3 = 0, flat = 0, chunk = 0;
     size_t off_w[6]{}, off_b[6]{}, off_s[6]{}, off_sb[6]{};
-    float *d_y1 = nullptr, *d_y2 = nullptr, *d_y3e = nullptr, *d_y3 = nullptr, *d_h1 = nullptr, *d_noise = nullptr;
+    float *d_y1 = nullptr, *d_y2 = nullptr, *d_y3e = nullptr, *d_y3 = nullptr, *d_h1 = nullptr;
 };
 
 namespace {
-std::string g_mactor_err;
 // layer shapes: conv1 (32, 2, 13, /5), conv2 (64, 32, 11, /4), conv3 (64, 64, 9, /4) (RL.py:36-45)
 constexpr int kC1 = 32, kC2 = 64, kC3 = 64;
 int conv_out(int n, int k, int s) { return (n - (k - 1) + (s - 1)) / s; }   // calculate_next_layer_dim (RL.py:49-50)
@@ -738,68 +654,41 @@ extern "C" {
 int qc_mactor_create(const qc_mdqn_params* p, int device, qc_mactor** out) {
     if (!out || !p) return QC_EINVAL;
     *out = nullptr;
-    auto fail = [](const char* m, int rc) {
-        std::lock_guard<std::mutex> lk(g_actor_mu);
-        g_mactor_err = m;
-        return rc;
-    };
-    if (p->n_actions < 1 || p->n_actions > 32) return fail("n_actions must be in [1, 32]", QC_EINVAL);
-    if (p->max_batch < 1) return fail("max_batch must be >= 1", QC_EINVAL);
+    if (const char* m = bad_net_size(-1, p->n_actions)) return g_mactor_err.fail(m, QC_EINVAL);
+    if (p->max_batch < 1) return g_mactor_err.fail("max_batch must be >= 1", QC_EINVAL);
+    const int T1 = conv_out(p->read_length, 13, 5), T2 = conv_out(T1, 11, 4), T3 = conv_out(T2, 9, 4);
+    if (p->read_length < 1 || T3 < 1)
+        return g_mactor_err.fail("read_length too short for the three convolutions", QC_EINVAL);
+    if ((uint64_t)(kC3 * T3) * (uint64_t)p->max_batch * sizeof(float) >= (1ull << 32))   // 32-bit buffer offsets
+        return g_mactor_err.fail("max_batch too large: fc1's operand [64 T3][max_batch] must stay below 4 GiB", QC_EINVAL);
+    if (const int rc = check_device(device, g_mactor_err, "the actor")) return rc;
     qc_mactor* a = new qc_mactor();
     a->p = *p;
     a->device = device;
-    a->T1 = conv_out(p->read_length, 13, 5);
-    a->T2 = conv_out(a->T1, 11, 4);
-    a->T3 = conv_out(a->T2, 9, 4);
-    if (p->read_length < 1 || a->T3 < 1) {
-        delete a;
-        return fail("read_length too short for the three convolutions", QC_EINVAL);
-    }
-    a->flat = kC3 * a->T3;
-    if ((uint64_t)a->flat * (uint64_t)p->max_batch * sizeof(float) >= (1ull << 32)) {   // 32-bit buffer offsets
-        delete a;
-        return fail("max_batch too large: fc1's operand [64 T3][max_batch] must stay below 4 GiB", QC_EINVAL);
-    }
-    a->noise_len = 2 * kH2 + kH3 + p->n_actions;
+    a->n_act = p->n_actions;
+    a->max_batch = p->max_batch;
+    a->seed = p->seed;
+    a->T1 = T1; a->T2 = T2; a->T3 = T3;
+    a->flat = kC3 * T3;
+    a->noise_len = noise_len(p->n_actions);
     a->chunk = (int)std::min<int64_t>(p->max_batch, p->chunk > 0 ? p->chunk : 2048);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        delete a;
-        return fail("no HIP device available (the actor has no CPU fallback)", QC_EHIP);
-    }
-    if (device < 0 || device >= ndev) {
-        delete a;
-        return fail("device index out of range", QC_EINVAL);
-    }
     const int O[6] = {kC1, kC2, kC3, kH2, kH3, p->n_actions};
     const int K[6] = {2 * 13, kC1 * 11, kC2 * 9, a->flat, kH2, kH3};
-    size_t off = 0;
-    for (int l = 0; l < 6; ++l) {
-        const size_t fr = (size_t)tiles(O[l]) * ksteps(K[l]) * 64, bp = (size_t)tiles(O[l]) * 32;
-        a->off_w[l] = off; off += fr;
-        a->off_b[l] = off; off += bp;
-        if (l >= 4) {
-            a->off_s[l] = off; off += fr;
-            a->off_sb[l] = off; off += bp;
-        }
-    }
+    const bool noisy[6] = {false, false, false, false, true, true};
+    const size_t floats = frag_layout(6, O, K, noisy, a->off_w, a->off_s, a->off_b, a->off_sb);
     Dev g(device);
     const size_t mb = (size_t)p->max_batch, ch = (size_t)a->chunk;
-    hipError_t e = hipMalloc(&a->d_w, off * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(a->d_w, 0, off * sizeof(float));
+    hipError_t e = hipMalloc(&a->d_w, floats * sizeof(float));
+    if (e == hipSuccess) e = hipMemset(a->d_w, 0, floats * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(&a->d_y1, ch * kC1 * a->T1 * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(&a->d_y2, ch * kC2 * a->T2 * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(&a->d_y3e, (size_t)a->flat * ch * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(&a->d_y3, (size_t)a->flat * mb * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(&a->d_h1, (size_t)kH2 * mb * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(&a->d_noise, (size_t)a->noise_len * mb * sizeof(float));
-    if (e == hipSuccess &&
-        hipFuncSetAttribute((const void*)k_actor_act, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (2 * kH1 * kE + 16 * 64) * (int)sizeof(float)) != hipSuccess)
-        e = hipErrorInvalidValue;
-    if (e != hipSuccess) {
+    if (e != hipSuccess || !enable_act_lds()) {
         qc_mactor_destroy(a);
-        return fail("device allocation failed", QC_ENOMEM);
+        return g_mactor_err.fail("device allocation failed", QC_ENOMEM);
     }
     *out = a;
     return QC_OK;
@@ -816,11 +705,7 @@ void qc_mactor_destroy(qc_mactor* a) {
     delete a;
 }
 
-const char* qc_mactor_last_error(const qc_mactor* a) {
-    if (a) return a->err.c_str();
-    std::lock_guard<std::mutex> lk(g_actor_mu);
-    return g_mactor_err.c_str();
-}
+const char* qc_mactor_last_error(const qc_mactor* a) { return a ? a->err.c_str() : g_mactor_err.text(); }
 
 int qc_mactor_set_stream(qc_mactor* a, void* stream) {
     if (!a) return QC_EINVAL;
@@ -833,36 +718,26 @@ int qc_mactor_flat_len(const qc_mactor* a) { return a ? a->flat : QC_EINVAL; }
 
 int qc_mactor_load(qc_mactor* a, const qc_dqn_layer layers[6]) {
     if (!a || !layers) return QC_EINVAL;
+    if (const int rc = validate_layers(layers, 6, kMactorRules, 3, a->err)) return rc;
     const int O[6] = {kC1, kC2, kC3, kH2, kH3, a->p.n_actions};
     const int K[6] = {2 * 13, kC1 * 11, kC2 * 9, a->flat, kH2, kH3};
-    for (int l = 0; l < 6; ++l) {
-        const qc_dqn_layer& L = layers[l];
-        if (!L.weight || !L.bias) { a->err = "layer " + std::to_string(l) + ": weight and bias are required"; return QC_EINVAL; }
-        if (l < 4 && (L.sigma_w || L.weight_norm)) {
-            a->err = "conv1..3 and fc1 are plain Conv1d / Linear layers (no weight_norm, no sigma)";
-            return QC_EINVAL;
-        }
-        if ((L.sigma_w == nullptr) != (L.sigma_b == nullptr)) { a->err = "sigma_w and sigma_b go together"; return QC_EINVAL; }
-        if (l >= 4 && !L.sigma_w && !L.weight_norm) { a->err = "fc21 / fc31: FactorizedNoisy or Linear_weight_normalize"; return QC_EINVAL; }
-    }
     Dev g(a->device);
     float* w = a->d_w;
     for (int l = 0; l < 6; ++l) {
         const qc_dqn_layer& L = layers[l];
-        const int Kp = (K[l] + 1) & ~1;
+        const int Kp = in_pad(K[l]);
+        const bool sigma = l >= 4 && L.sigma_w;
         hipLaunchKernelGGL(k_actor_prep, dim3(1), dim3(1024), 0, a->stream, L.weight, L.weight_norm, O[l], K[l], Kp,
                            w + a->off_w[l], L.bias, w + a->off_b[l], l < 3 ? 1 : 0);
-        if (l >= 4 && L.sigma_w)
+        if (sigma)
             hipLaunchKernelGGL(k_actor_prep, dim3(1), dim3(1024), 0, a->stream, L.sigma_w, (const float*)nullptr, O[l],
                                K[l], Kp, w + a->off_s[l], L.sigma_b, w + a->off_sb[l], 0);
+        if (l >= 4)   // fc21 / fc31 are k_actor_act's layers 2 / 3
+            a->L[l - 2] = Layer{w + a->off_w[l], sigma ? w + a->off_s[l] : nullptr, w + a->off_b[l],
+                                sigma ? w + a->off_sb[l] : nullptr};
     }
-    a->has_s21 = layers[4].sigma_w != nullptr;
-    a->has_s31 = layers[5].sigma_w != nullptr;
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        a->err = std::string("measurement actor weight preparation: ") + hipGetErrorString(e);
-        return QC_EHIP;
-    }
+    if (e != hipSuccess) return hip_fail(a->err, e, "measurement actor weight preparation");
     a->loaded = true;
     return QC_OK;
 }
@@ -898,48 +773,11 @@ int qc_mactor_act(qc_mactor* a, int64_t B, int64_t env_offset, const float* obs,
         hipLaunchKernelGGL((k_mfc<kMfcMT, kMfcNT>), dim3((unsigned)((B + envs_per_wg - 1) / envs_per_wg)), dim3(256), 0,
                            a->stream, a->d_y3, ld, a->flat, w + a->off_w[3], w + a->off_b[3], a->d_h1, B);
     }
-    const bool need_noise = noisy && (a->has_s21 || a->has_s31);
-    if (need_noise) {
-        if (noise) {
-            const int64_t n = B * a->noise_len;
-            hipLaunchKernelGGL(k_actor_transpose, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, a->stream, noise,
-                               a->d_noise, ld, B, a->noise_len);
-        } else {
-            hipLaunchKernelGGL(k_actor_noise, dim3((unsigned)((B + 255) / 256), (unsigned)((a->noise_len + 1) / 2)),
-                               dim3(256), 0, a->stream, a->d_noise, ld, B, a->noise_len, env_offset, a->p.seed, counter);
-        }
-    }
     ActArgs k{};
-    k.L[2].u = w + a->off_w[4];
-    k.L[2].ub = w + a->off_b[4];
-    k.L[2].s = a->has_s21 ? w + a->off_s[4] : nullptr;
-    k.L[2].sb = a->has_s21 ? w + a->off_sb[4] : nullptr;
-    k.L[3].u = w + a->off_w[5];
-    k.L[3].ub = w + a->off_b[5];
-    k.L[3].s = a->has_s31 ? w + a->off_s[5] : nullptr;
-    k.L[3].sb = a->has_s31 ? w + a->off_sb[5] : nullptr;
-    k.n_act = a->p.n_actions;
-    k.B = B;
-    k.env_offset = env_offset;
-    k.noisy = need_noise ? 1 : 0;
-    k.noise = a->d_noise;
-    k.noise_ld = ld;
-    k.eps = (float)eps;
-    k.seed = a->p.seed;
-    k.counter = counter;
-    k.actions = actions;
-    k.q_out = q_out;
-    k.random_out = random_out;
     k.h_in = a->d_h1;
     k.h_ld = ld;
-    hipLaunchKernelGGL(k_actor_act, dim3((unsigned)((B + kE - 1) / kE)), dim3(kThreads),
-                       (2 * kH1 * kE + 16 * 64) * sizeof(float), a->stream, k);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) {
-        a->err = std::string("measurement actor launch: ") + hipGetErrorString(e);
-        return QC_EHIP;
-    }
-    return QC_OK;
+    return act_tail(a, k, "measurement actor launch", B, env_offset, noisy, noise, eps, counter, actions, q_out,
+                    random_out);
 }
 
 }  // extern "C"

@@ -1,0 +1,112 @@
+// qcart_dqn.hpp — the one device-side definition of the reference's direct_DQN (RL.py:80-111, layers.py)
+// that the actor (qcart_actor.hip) and the learner (qcart_learner.hip) share: the network constants and
+// noise layout, the dense layer of a 4-wave workgroup on the fragments of qcart_mfma.hpp, the fc41 wave
+// split, the NoisyNet noise draw, the 1024-thread tree sum and the weight-norm scale.
+//
+// One workgroup = 32 columns (envs / batch rows) x 4 waves; activations live in LDS as [feature][32] and
+// never leave the CU. A factorised noisy layer is two GEMMs per tile, u_w X and sigma_w (eps_in o X):
+//   y = u_w x + u_b + eps_out o (sigma_w (eps_in o x) + sigma_b)   (== (u_w + sigma_w o eps_out eps_in^T) x + ...)
+// The kernels' epilogues spell that sum themselves: how it is written fixes its rounding (-ffp-contract=on).
+#pragma once
+#include "qcart_kernels.hpp"
+#include "qcart_mfma.hpp"
+
+namespace qcart {
+namespace dqn {
+
+using namespace qcart::mfma;   // kE, f32x16, tiles / ksteps, gemm_tile, drow
+
+constexpr int kH1 = 512, kH2 = 256, kH3 = 256, kHM = 128;   // fc1, fc2, fc31, fc32 widths
+constexpr int kMaxIn = 512;      // data_length limit (LDS: [in][32] fp32 within 64 KiB)
+constexpr int kThreads = 256;    // 4 waves
+__host__ __device__ constexpr int in_pad(int data_length) { return (data_length + 1) & ~1; }
+// the create-time range checks (data_length < 0: the handle has none); null when the sizes are fine
+inline const char* bad_net_size(int data_length, int n_actions) {
+    static_assert(kMaxIn == 512, "the text below names the limit");
+    if (data_length >= 0 && (data_length < 1 || data_length > kMaxIn)) return "data_length must be in [1, 512]";
+    if (n_actions < 1 || n_actions > 32) return "n_actions must be in [1, 32]";
+    return nullptr;
+}
+
+// one noise sample, as FactorizedNoisy draws it: eps_in / eps_out of fc31, then of fc41 (n_actions long)
+constexpr int kEpsIn31 = 0, kEpsOut31 = kEpsIn31 + kH2, kEpsIn41 = kEpsOut31 + kH3, kEpsOut41 = kEpsIn41 + kH3;
+__host__ __device__ constexpr int noise_len(int n_actions) { return kEpsOut41 + n_actions; }
+
+// k_actor_act's LDS: RA = H1 [512][32], later H3 + eps_in o H3; RB = X0 [in_pad][32], later H2 + eps_in o H2;
+// RC = fc41's sigma partial as D registers [16][64]
+constexpr int kActLdsFloats = 2 * kH1 * kE + 16 * 64;
+constexpr size_t kActLdsBytes = kActLdsFloats * sizeof(float);
+
+// Y = W X for one layer, on 4 waves: wave w takes the output tiles w, w + 4, ... (X: LDS [K][32]); where sf is
+// given, also Ys = sigma_w Xe on the sigma fragments. epi(o, y_u, y_sigma) gets each of the lane's 16 D
+// elements (output o, column lane & 31) and adds bias / noise, applies ReLU, stores.
+template <class Epi>
+__device__ __forceinline__ void dense4(const float* __restrict__ uf, const float* __restrict__ sf, const float* x,
+                                       const float* xe, int O, int K, int lane, int wave, Epi epi) {
+    const int S = ksteps(K);
+    for (int t = wave; t < tiles(O); t += 4) {
+        f32x16 acc = {}, accs = {};
+        gemm_tile(acc, uf + (size_t)t * S * 64, x, S, lane);
+        if (sf) gemm_tile(accs, sf + (size_t)t * S * 64, xe, S, lane);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) epi(t * 32 + drow(r, lane), acc[r], accs[r]);
+    }
+}
+
+// fc41, one 32-row tile: wave 0 computes u_w H3, wave 1 sigma_w (eps_in o H3), handed over through the LDS
+// partial rc. Every wave must call it (it holds a barrier); only wave 0 returns true, after epi(o, y_u, y_sigma)
+// for each of its lane's outputs o = drow(r, lane) < n_act. Waves 2 and 3 may run `other` beside the two GEMMs.
+template <class Epi, class Other>
+__device__ __forceinline__ bool fc41(const float* __restrict__ uf, const float* __restrict__ sf, const float* h3,
+                                     const float* h3e, float* rc, int n_act, int lane, int wave, Epi epi,
+                                     Other other) {
+    if (wave == 1 && sf) {
+        f32x16 accs = {};
+        gemm_tile(accs, sf, h3e, ksteps(kH3), lane);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) rc[r * 64 + lane] = accs[r];
+    }
+    f32x16 acc = {};
+    if (wave == 0) gemm_tile(acc, uf, h3, ksteps(kH3), lane);
+    if (wave >= 2) other();
+    __syncthreads();
+    if (wave != 0) return false;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const int o = drow(r, lane);
+        if (o < n_act) epi(o, acc[r], sf ? rc[r * 64 + lane] : 0.f);
+    }
+    return true;
+}
+
+// NoisyNet noise pair `pair` of stream `key` (an env, or a learner chunk): f(z) = sign(z) sqrt|z|
+// (layers.py:77-79) of two Philox normals keyed by (seed, key), counter, tag 0x100 + pair. Box-Muller in fp32
+// (hardware log / sin / cos): the network noise is fp32 and has no oracle stream
+__device__ __forceinline__ float2 noise_pair(uint64_t seed, uint64_t counter, uint32_t key, int pair) {
+    uint32_t c[4] = {(uint32_t)counter, (uint32_t)(counter >> 32), key, 0x100u + (uint32_t)pair};
+    philox10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    const float u1 = ((float)(c[0] >> 8) + 0.5f) * 0x1.0p-24f, u2 = (float)(c[1] >> 8) * 0x1.0p-24f;
+    const float rad = sqrtf(-2.f * __logf(u1));
+    float sn, cs;
+    __sincosf(6.283185307f * u2, &sn, &cs);
+    const float f0 = rad * cs, f1 = rad * sn;
+    return float2{copysignf(sqrtf(fabsf(f0)), f0), copysignf(sqrtf(fabsf(f1)), f1)};
+}
+
+// sum of v over a 1024-thread workgroup in a fixed order (halving from 512, partner + w); part: LDS [1024]
+template <class T>
+__device__ __forceinline__ T block_sum(T v, T* part) {
+    part[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = 512; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    return part[0];
+}
+
+// Linear_weight_normalize (layers.py:97-103): W_eff = W g / ||W||_F, from g and ss = sum W^2
+__device__ __forceinline__ float wn_scale(float g, double ss) { return (float)((double)g / sqrt(ss)); }
+
+}  // namespace dqn
+}  // namespace qcart

@@ -5,9 +5,8 @@
 // Launches per update (plain launches on the handle's stream, no atomics on any gradient, so the same
 // inputs give bit-identical parameters):
 //   1 k_learner_noise  the 32 chunks' noise (injected, or Philox) -> feature-major [noise_len][32]
-//   2 k_learner_fwd    3 B/32 workgroups: online/next, online/prev, target/next. The actor's shape (32 rows
-//                      x 4 waves, activations in LDS as [feature][32], every GEMM on v_mfma_f32_32x32x2_f32
-//                      from fragment-ordered weights) plus the mean head fc32 / fc42; the online/prev pass
+//   2 k_learner_fwd    3 B/32 workgroups: online/next, online/prev, target/next. The network of qcart_dqn.hpp
+//                      (the actor's) plus the mean head fc32 / fc42; the online/prev pass
 //                      also writes X, h1, h2, a3, r32 and the eps_in-scaled h2 / a3 feature-major to HBM
 //   3 k_learner_loss   one workgroup: argmax (first index on ties), gathers, ul, dQ, dm, the loss sum
 //   4 k_learner_bwd    B/32 workgroups: dX = W^T dY down the net from transposed fragments, ReLU masks from
@@ -22,24 +21,20 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/qcart.h"
-#include "qcart_kernels.hpp"
-#include "qcart_mfma.hpp"
+#include "qcart_dqn.hpp"
+#include "qcart_host.hpp"
 
 namespace qcart {
 namespace learner {
 
-using namespace qcart::mfma;
-constexpr int kH1 = 512, kH2 = 256, kH3 = 256, kHM = 128;   // fc1, fc2, fc31, fc32 widths
-constexpr int kMaxIn = 512;
-constexpr int kThreads = 256;
+using namespace qcart::dqn;
 constexpr int kChunks = 32;        // FactorizedNoisy.forward: n = 32 noise samples per batch (layers.py:58)
 constexpr int kNT = 20;            // parameter tensors
-constexpr int kLdsFloats = 2 * kH1 * kE + 16 * 64 + kHM * kE;
+constexpr int kLdsFloats = kActLdsFloats + kHM * kE;   // the actor's plan, then R32 [128][32]
 
 // offsets into the fragment buffer (floats): forward part first (copied to the target), then transposed
 struct FragOff {
@@ -86,99 +81,64 @@ __global__ __launch_bounds__(kThreads) void k_learner_fwd(const LArgs a) {
     }
     __syncthreads();
 
-    // ---- fc1: 16 tiles, 4 per wave; ReLU
-    for (int t = wave; t < tiles(kH1); t += 4) {
-        f32x16 acc = {};
-        gemm_tile(acc, F + a.fo.u[0] + (size_t)t * ksteps(a.in_pad) * 64, RB, ksteps(a.in_pad), lane);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int o = t * 32 + drow(r, lane);
-            const float h = fmaxf(acc[r] + F[a.fo.ub[0] + o], 0.f);
-            RA[o * kE + env] = h;
-            if (ws) a.H1[(size_t)o * B + eg] = h;
-        }
-    }
+    // ---- fc1: ReLU
+    dense4(F + a.fo.u[0], nullptr, RB, nullptr, kH1, a.in_pad, lane, wave, [&](int o, float y, float) {
+        const float h = fmaxf(y + F[a.fo.ub[0] + o], 0.f);
+        RA[o * kE + env] = h;
+        if (ws) a.H1[(size_t)o * B + eg] = h;
+    });
     __syncthreads();
 
-    // ---- fc2: 8 tiles, 2 per wave; ReLU; eps_in(fc31) o H2
+    // ---- fc2: ReLU; eps_in(fc31) o H2
     float* H2 = RB;
     float* H2e = RB + kH2 * kE;
-    for (int t = wave; t < tiles(kH2); t += 4) {
-        f32x16 acc = {};
-        gemm_tile(acc, F + a.fo.u[1] + (size_t)t * ksteps(kH1) * 64, RA, ksteps(kH1), lane);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int o = t * 32 + drow(r, lane);
-            const float h = fmaxf(acc[r] + F[a.fo.ub[1] + o], 0.f);
-            const float he = h * nz(a, o, eg);
-            H2[o * kE + env] = h;
-            H2e[o * kE + env] = he;
-            if (ws) {
-                a.H2[(size_t)o * B + eg] = h;
-                a.H2e[(size_t)o * B + eg] = he;
-            }
+    dense4(F + a.fo.u[1], nullptr, RA, nullptr, kH2, kH1, lane, wave, [&](int o, float y, float) {
+        const float h = fmaxf(y + F[a.fo.ub[1] + o], 0.f);
+        const float he = h * nz(a, kEpsIn31 + o, eg);
+        H2[o * kE + env] = h;
+        H2e[o * kE + env] = he;
+        if (ws) {
+            a.H2[(size_t)o * B + eg] = h;
+            a.H2e[(size_t)o * B + eg] = he;
         }
-    }
+    });
     __syncthreads();
 
-    // ---- fc31 (noisy): 8 tiles, 2 per wave; ReLU; eps_in(fc41) o H3
+    // ---- fc31 (noisy): ReLU; eps_in(fc41) o H3
     float* H3 = RA;
     float* H3e = RA + kH3 * kE;
-    for (int t = wave; t < tiles(kH3); t += 4) {
-        f32x16 acc = {}, accs = {};
-        gemm_tile(acc, F + a.fo.u[2] + (size_t)t * ksteps(kH2) * 64, H2, ksteps(kH2), lane);
-        gemm_tile(accs, F + a.fo.s[2] + (size_t)t * ksteps(kH2) * 64, H2e, ksteps(kH2), lane);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int o = t * 32 + drow(r, lane);
-            const float y = acc[r] + F[a.fo.ub[2] + o] + nz(a, kH2 + o, eg) * (accs[r] + F[a.fo.sb[2] + o]);
-            const float h = fmaxf(y, 0.f);
-            const float he = h * nz(a, 2 * kH2 + o, eg);
-            H3[o * kE + env] = h;
-            H3e[o * kE + env] = he;
-            if (ws) {
-                a.A3[(size_t)o * B + eg] = h;
-                a.A3e[(size_t)o * B + eg] = he;
-            }
+    dense4(F + a.fo.u[2], F + a.fo.s[2], H2, H2e, kH3, kH2, lane, wave, [&](int o, float yu, float ys) {
+        const float y = yu + F[a.fo.ub[2] + o] + nz(a, kEpsOut31 + o, eg) * (ys + F[a.fo.sb[2] + o]);
+        const float h = fmaxf(y, 0.f);
+        const float he = h * nz(a, kEpsIn41 + o, eg);
+        H3[o * kE + env] = h;
+        H3e[o * kE + env] = he;
+        if (ws) {
+            a.A3[(size_t)o * B + eg] = h;
+            a.A3e[(size_t)o * B + eg] = he;
         }
-    }
+    });
     // ---- fc32 (mean head): 4 tiles, 1 per wave; ReLU (the next-state argmax pass needs no mean)
-    if (pass != 0) {
-        f32x16 acc = {};
-        gemm_tile(acc, F + a.fo.u[4] + (size_t)wave * ksteps(kH2) * 64, H2, ksteps(kH2), lane);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int o = wave * 32 + drow(r, lane);
-            const float h = fmaxf(acc[r] + F[a.fo.ub[4] + o], 0.f);
+    if (pass != 0)
+        dense4(F + a.fo.u[4], nullptr, H2, nullptr, kHM, kH2, lane, wave, [&](int o, float y, float) {
+            const float h = fmaxf(y + F[a.fo.ub[4] + o], 0.f);
             RD[o * kE + env] = h;
             if (ws) a.R32[(size_t)o * B + eg] = h;
-        }
-    }
+        });
     __syncthreads();
 
-    // ---- fc41: wave 0 u_w H3, wave 1 sigma_w (eps_in o H3) -> LDS partial; fc42: wave 2 (row 0 of its tile)
-    f32x16 acc = {};
-    if (wave == 1) {
-        gemm_tile(acc, F + a.fo.s[3], H3e, ksteps(kH3), lane);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) RC[r * 64 + lane] = acc[r];
-    } else if (wave == 0) {
-        gemm_tile(acc, F + a.fo.u[3], H3, ksteps(kH3), lane);
-    } else if (wave == 2 && pass != 0) {
-        gemm_tile(acc, F + a.fo.u[5], RD, ksteps(kHM), lane);
-        if (lane < 32) a.M[(size_t)pass * B + eg] = acc[0] + F[a.fo.ub[5]];
-    }
-    __syncthreads();
-    if (wave != 0) return;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int o = drow(r, lane);
-        if (o < a.n_act) {
-            const float q = acc[r] + F[a.fo.ub[3] + o] +
-                            nz(a, 2 * kH2 + kH3 + o, eg) * (RC[r * 64 + lane] + F[a.fo.sb[3] + o]);
-            a.Q[((size_t)pass * B + eg) * 32 + o] = q;
-        }
-    }
+    // ---- fc41 -> Q; beside it fc42 on wave 2 (row 0 of its tile) -> M
+    fc41(F + a.fo.u[3], F + a.fo.s[3], H3, H3e, RC, a.n_act, lane, wave,
+         [&](int o, float yu, float ys) {
+             a.Q[((size_t)pass * B + eg) * 32 + o] =
+                 yu + F[a.fo.ub[3] + o] + nz(a, kEpsOut41 + o, eg) * (ys + F[a.fo.sb[3] + o]);
+         },
+         [&] {
+             if (wave != 2 || pass == 0) return;
+             f32x16 m = {};
+             gemm_tile(m, F + a.fo.u[5], RD, ksteps(kHM), lane);
+             if (lane < 32) a.M[(size_t)pass * B + eg] = m[0] + F[a.fo.ub[5]];
+         });
 }
 
 struct LossArgs {
@@ -232,17 +192,12 @@ __global__ __launch_bounds__(1024) void k_learner_loss(const LossArgs a) {
         for (int j = 0; j < 32; ++j) {
             const float g = j < a.n_act ? delta * ((j == act ? 1.f : 0.f) - a.inv_A) : 0.f;
             a.dQ[(size_t)j * a.B + b] = g;
-            a.dQe[(size_t)j * a.B + b] = j < a.n_act ? g * a.noise[(2 * kH2 + kH3 + j) * kChunks + c] : 0.f;
+            a.dQe[(size_t)j * a.B + b] = j < a.n_act ? g * a.noise[(kEpsOut41 + j) * kChunks + c] : 0.f;
         }
     }
-    part[threadIdx.x] = lsum;
-    __syncthreads();
-    for (int w = 512; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
-        __syncthreads();
-    }
+    lsum = block_sum(lsum, part);
     if (threadIdx.x == 0) {
-        const float loss = part[0] * a.inv_B;
+        const float loss = lsum * a.inv_B;
         a.loss[0] = loss;
         if (a.loss_user) a.loss_user[0] = loss;
         if (!isfinite(loss)) a.cnt[0] += 1;
@@ -278,21 +233,14 @@ __global__ __launch_bounds__(kThreads) void k_learner_bwd(const LArgs a) {
     __syncthreads();
 
     // ---- fc41^T: dA3 = u_w^T dQ + eps_in o (sigma_w^T (eps_out o dQ)); ReLU mask of a3
-    for (int t = wave; t < tiles(kH3); t += 4) {
-        f32x16 acc = {}, accs = {};
-        gemm_tile(acc, F + a.fo.t41u + (size_t)t * 16 * 64, DQ, 16, lane);
-        gemm_tile(accs, F + a.fo.t41s + (size_t)t * 16 * 64, DQe, 16, lane);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int o = t * 32 + drow(r, lane);
-            const float g = a.A3[(size_t)o * B + eg] > 0.f ? acc[r] + nz(a, 2 * kH2 + o, eg) * accs[r] : 0.f;
-            const float ge = g * nz(a, kH2 + o, eg);
-            D3[o * kE + env] = g;
-            D3e[o * kE + env] = ge;
-            a.dZ3[(size_t)o * B + eg] = g;
-            a.dZ3e[(size_t)o * B + eg] = ge;
-        }
-    }
+    dense4(F + a.fo.t41u, F + a.fo.t41s, DQ, DQe, kH3, 32, lane, wave, [&](int o, float yu, float ys) {
+        const float g = a.A3[(size_t)o * B + eg] > 0.f ? yu + nz(a, kEpsIn41 + o, eg) * ys : 0.f;
+        const float ge = g * nz(a, kEpsOut31 + o, eg);
+        D3[o * kE + env] = g;
+        D3e[o * kE + env] = ge;
+        a.dZ3[(size_t)o * B + eg] = g;
+        a.dZ3e[(size_t)o * B + eg] = ge;
+    });
     __syncthreads();
 
     // ---- fc31^T and fc32^T meet in h2: dH2 = u_w^T dZ3 + W32_eff^T dZ32 + eps_in o (sigma_w^T dZ3e)
@@ -304,7 +252,7 @@ __global__ __launch_bounds__(kThreads) void k_learner_bwd(const LArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int o = t * 32 + drow(r, lane);
-            const float g = a.H2[(size_t)o * B + eg] > 0.f ? acc[r] + nz(a, o, eg) * accs[r] : 0.f;
+            const float g = a.H2[(size_t)o * B + eg] > 0.f ? acc[r] + nz(a, kEpsIn31 + o, eg) * accs[r] : 0.f;
             D2[o * kE + env] = g;
             a.dZ2[(size_t)o * B + eg] = g;
         }
@@ -312,15 +260,9 @@ __global__ __launch_bounds__(kThreads) void k_learner_bwd(const LArgs a) {
     __syncthreads();
 
     // ---- fc2^T: dH1 = W2_eff^T dZ2; ReLU mask of h1
-    for (int t = wave; t < tiles(kH1); t += 4) {
-        f32x16 acc = {};
-        gemm_tile(acc, F + a.fo.t2 + (size_t)t * ksteps(kH2) * 64, D2, ksteps(kH2), lane);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int o = t * 32 + drow(r, lane);
-            a.dZ1[(size_t)o * B + eg] = a.H1[(size_t)o * B + eg] > 0.f ? acc[r] : 0.f;
-        }
-    }
+    dense4(F + a.fo.t2, nullptr, D2, nullptr, kH1, kH2, lane, wave, [&](int o, float y, float) {
+        a.dZ1[(size_t)o * B + eg] = a.H1[(size_t)o * B + eg] > 0.f ? y : 0.f;
+    });
 }
 
 // dW = dY X^T: A = dY [O pad 32][B], X [K pad 32][B] (feature-major, pad rows zero), out [O][K] natural layout
@@ -391,14 +333,9 @@ __global__ __launch_bounds__(1024) void k_learner_wndot(const float* __restrict_
     const Tensor T = tt.t[ti];
     double s = 0.0;
     for (int i = threadIdx.x; i < T.n; i += 1024) s += (double)G[T.off + i] * (double)P[T.off + i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    for (int w = 512; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
-        __syncthreads();
-    }
+    s = block_sum(s, part);
     if (threadIdx.x == 0) {
-        dot[T.wn] = part[0];
+        dot[T.wn] = s;
         dot[4 + T.wn] = (double)P[tt.t[ti + 2].off];   // g before the step: the optimizer updates it in the same launch as W
     }
 }
@@ -465,14 +402,9 @@ __global__ __launch_bounds__(1024) void k_learner_prep(const float* __restrict__
     if (J.g_off >= 0) {
         for (int i = threadIdx.x; i < J.O * J.K; i += 1024) ss += (double)W[i] * (double)W[i];
     }
-    part[threadIdx.x] = ss;
-    __syncthreads();
-    for (int w = 512; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
-        __syncthreads();
-    }
-    const float sc = J.g_off >= 0 ? (float)((double)P[J.g_off] / sqrt(part[0])) : 1.f;
-    if (J.mode == 0 && J.wn >= 0 && blockIdx.y == 0 && threadIdx.x == 0) norm[J.wn] = (float)sqrt(part[0]);
+    ss = block_sum(ss, part);
+    const float sc = J.g_off >= 0 ? wn_scale(P[J.g_off], ss) : 1.f;
+    if (J.mode == 0 && J.wn >= 0 && blockIdx.y == 0 && threadIdx.x == 0) norm[J.wn] = (float)sqrt(ss);
     float* out = F + J.out_off;
     const int first = blockIdx.y * 1024 + threadIdx.x, stride = kPrepParts * 1024;
     if (J.mode == 2) {
@@ -503,21 +435,16 @@ __global__ __launch_bounds__(256) void k_learner_noise(const float* __restrict__
     const int np = (noise_len + 1) / 2;
     if (i >= kChunks * np) return;
     const int c = i % kChunks, p = i / kChunks;
-    uint32_t k[4] = {(uint32_t)counter, (uint32_t)(counter >> 32), (uint32_t)c, 0x100u + (uint32_t)p};
-    philox10(k, (uint32_t)seed, (uint32_t)(seed >> 32));
-    const float u1 = ((float)(k[0] >> 8) + 0.5f) * 0x1.0p-24f, u2 = (float)(k[1] >> 8) * 0x1.0p-24f;
-    const float rad = sqrtf(-2.f * __logf(u1));
-    float sn, cs;
-    __sincosf(6.283185307f * u2, &sn, &cs);
-    const float f0 = rad * cs, f1 = rad * sn;
-    out[(2 * p) * kChunks + c] = copysignf(sqrtf(fabsf(f0)), f0);
-    if (2 * p + 1 < noise_len) out[(2 * p + 1) * kChunks + c] = copysignf(sqrtf(fabsf(f1)), f1);
+    const float2 f = noise_pair(seed, counter, (uint32_t)c, p);
+    out[(2 * p) * kChunks + c] = f.x;
+    if (2 * p + 1 < noise_len) out[(2 * p + 1) * kChunks + c] = f.y;
 }
 
 }  // namespace learner
 }  // namespace qcart
 
 using namespace qcart::learner;
+using namespace qcart::host;
 
 struct qc_learner {
     qc_learner_params p{};
@@ -552,24 +479,7 @@ struct qc_learner {
 };
 
 namespace {
-std::mutex g_learner_mu;
-std::string g_learner_err;
-
-struct Dev {
-    int prev = -1;
-    explicit Dev(int d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != d) (void)hipSetDevice(d);
-    }
-    ~Dev() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-int hip_fail(qc_learner* l, hipError_t e, const char* what) {
-    l->err = std::string(what) + ": " + hipGetErrorString(e);
-    return QC_EHIP;
-}
+CreateError g_learner_err;
 
 constexpr double kBeta1 = 0.9, kBeta2 = 0.9995, kEps = 1e-15;   // RL.py:145
 constexpr int kCenteredAfter = 10;                               // optimizer.py:9
@@ -577,6 +487,22 @@ constexpr int kCenteredAfter = 10;                               // optimizer.py
 // tensor indices of layer l (fc1, fc2, fc31, fc41, fc32, fc42): weight, bias, then g | sigma_w, sigma_b
 constexpr int kFirst[6] = {0, 3, 6, 10, 14, 17};
 constexpr bool kNoisy[6] = {false, false, true, true, false, false};
+constexpr LayerRule kLearnerRules[] = {
+    {0b001100, states_where([](bool wn, bool sw, bool sb) { return !sw || !sb || wn; }),
+     "fc31 / fc41 are FactorizedNoisy layers (sigma_w and sigma_b, no weight_norm): the learner "
+     "implements direct_DQN(noisy_layers=2)"},
+    {0b110011, states_where([](bool wn, bool sw, bool sb) { return !wn || sw || sb; }),
+     "fc1 / fc2 / fc32 / fc42 are Linear_weight_normalize layers (weight_norm, no sigma)"},
+};
+
+// the six layers' tensors inside one flat buffer (the parameters, the target's, or the gradients)
+void layer_views(const qc_learner* l, const float* base, qc_dqn_layer out[6]) {
+    for (int j = 0; j < 6; ++j) {
+        const Tensor* T = &l->tt.t[kFirst[j]];
+        out[j] = qc_dqn_layer{base + T[0].off, base + T[1].off, kNoisy[j] ? nullptr : base + T[2].off,
+                              kNoisy[j] ? base + T[2].off : nullptr, kNoisy[j] ? base + T[3].off : nullptr};
+    }
+}
 
 void free_all(qc_learner* l) {
     for (void* q : {(void*)l->P, (void*)l->PT, (void*)l->G, (void*)l->E, (void*)l->V, (void*)l->MU, (void*)l->F,
@@ -614,31 +540,23 @@ extern "C" {
 int qc_learner_create(const qc_learner_params* p, int device, qc_learner** out) {
     if (!out || !p) return QC_EINVAL;
     *out = nullptr;
-    auto fail = [](const char* m, int rc) {
-        std::lock_guard<std::mutex> lk(g_learner_mu);
-        g_learner_err = m;
-        return rc;
-    };
-    if (p->data_length < 1 || p->data_length > kMaxIn) return fail("data_length must be in [1, 512]", QC_EINVAL);
-    if (p->n_actions < 1 || p->n_actions > 32) return fail("n_actions must be in [1, 32]", QC_EINVAL);
+    auto fail = [](const char* m, int rc) { return g_learner_err.fail(m, rc); };
+    if (const char* m = bad_net_size(p->data_length, p->n_actions)) return fail(m, QC_EINVAL);
     if (p->batch_size < 128 || p->batch_size > 4096 || p->batch_size % 128 != 0)
         return fail("batch_size must be a multiple of 128 in [128, 4096]: the learner implements FactorizedNoisy's "
                     "32-chunk noise branch (layers.py:57-74), not the per-row branch of other batch sizes",
                     QC_EINVAL);
     if (p->backup_period < 1) return fail("backup_period must be >= 1", QC_EINVAL);
     if (!(p->lr >= 0.)) return fail("lr must be >= 0", QC_EINVAL);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail("no HIP device available (the learner has no CPU fallback)", QC_EHIP);
-    if (device < 0 || device >= ndev) return fail("device index out of range", QC_EINVAL);
+    if (const int rc = check_device(device, g_learner_err, "the learner")) return rc;
 
     qc_learner* l = new qc_learner();
     l->p = *p;
     l->device = device;
     l->lr = p->lr;
     const int L = l->L = p->data_length, A = l->A = p->n_actions, B = l->B = p->batch_size;
-    l->in_pad = (L + 1) & ~1;
-    l->noise_len = 2 * kH2 + kH3 + A;
+    l->in_pad = in_pad(L);
+    l->noise_len = noise_len(A);
 
     // ---- parameter tensors (offsets in multiples of 4 floats)
     const int O[6] = {kH1, kH2, kH3, A, kHM, 1};
@@ -672,14 +590,7 @@ int qc_learner_create(const qc_learner_params* p, int device, qc_learner** out) 
 
     // ---- fragment buffer: forward fragments and padded biases, then the transposed fragments
     const int Kp[6] = {l->in_pad, kH1, kH2, kH3, kH2, kHM};
-    int fo = 0;
-    for (int j = 0; j < 6; ++j) {
-        const int fr = tiles(O[j]) * ksteps(Kp[j]) * 64, bp = tiles(O[j]) * 32;
-        l->fo.u[j] = fo; fo += fr;
-        l->fo.s[j] = fo; fo += kNoisy[j] ? fr : 0;
-        l->fo.ub[j] = fo; fo += bp;
-        l->fo.sb[j] = fo; fo += kNoisy[j] ? bp : 0;
-    }
+    int fo = frag_layout(6, O, Kp, kNoisy, l->fo.u, l->fo.s, l->fo.ub, l->fo.sb);
     l->nf_fwd = fo;
     auto tfrag = [&](int j, int kpad) {   // fragments of W_j^T: [K_j rows][O_j pad kpad]
         const int at = fo;
@@ -814,11 +725,7 @@ void qc_learner_destroy(qc_learner* l) {
     delete l;
 }
 
-const char* qc_learner_last_error(const qc_learner* l) {
-    if (l) return l->err.c_str();
-    std::lock_guard<std::mutex> lk(g_learner_mu);
-    return g_learner_err.c_str();
-}
+const char* qc_learner_last_error(const qc_learner* l) { return l ? l->err.c_str() : g_learner_err.text(); }
 
 int qc_learner_set_stream(qc_learner* l, void* stream) {
     if (!l) return QC_EINVAL;
@@ -830,19 +737,7 @@ int qc_learner_noise_len(const qc_learner* l) { return l ? l->noise_len : QC_EIN
 
 int qc_learner_load(qc_learner* l, const qc_dqn_layer layers[6]) {
     if (!l || !layers) return QC_EINVAL;
-    for (int j = 0; j < 6; ++j) {
-        const qc_dqn_layer& Y = layers[j];
-        if (!Y.weight || !Y.bias) { l->err = "layer " + std::to_string(j) + ": weight and bias are required"; return QC_EINVAL; }
-        if (kNoisy[j] && (!Y.sigma_w || !Y.sigma_b || Y.weight_norm)) {
-            l->err = "fc31 / fc41 are FactorizedNoisy layers (sigma_w and sigma_b, no weight_norm): the learner "
-                     "implements direct_DQN(noisy_layers=2)";
-            return QC_EINVAL;
-        }
-        if (!kNoisy[j] && (!Y.weight_norm || Y.sigma_w || Y.sigma_b)) {
-            l->err = "fc1 / fc2 / fc32 / fc42 are Linear_weight_normalize layers (weight_norm, no sigma)";
-            return QC_EINVAL;
-        }
-    }
+    if (const int rc = validate_layers(layers, 6, kLearnerRules, 2, l->err)) return rc;
     Dev g(l->device);
     hipError_t e = hipSuccess;
     auto put = [&](int ti, const float* src) {
@@ -864,11 +759,11 @@ int qc_learner_load(qc_learner* l, const qc_dqn_layer layers[6]) {
     const size_t pb = (size_t)l->np * sizeof(float);
     for (float* q : {l->E, l->V, l->MU, l->G})
         if (e == hipSuccess) e = hipMemsetAsync(q, 0, pb, l->stream);
-    if (e != hipSuccess) return hip_fail(l, e, "learner parameter copy");
+    if (e != hipSuccess) return hip_fail(l->err, e, "learner parameter copy");
     hipLaunchKernelGGL(k_learner_prep, dim3(l->nprep, kPrepParts), dim3(1024), 0, l->stream, l->P, l->F, l->d_prep,
                        l->d_norm);
     e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(l, e, "learner weight preparation");
+    if (e != hipSuccess) return hip_fail(l->err, e, "learner weight preparation");
     l->step = 0;
     l->l1 = l->l2 = 0.;
     l->backup_counter = 0;
@@ -878,23 +773,13 @@ int qc_learner_load(qc_learner* l, const qc_dqn_layer layers[6]) {
 
 int qc_learner_layers(qc_learner* l, int target, qc_dqn_layer out[6]) {
     if (!l || !out) return QC_EINVAL;
-    const float* base = target ? l->PT : l->P;
-    for (int j = 0; j < 6; ++j) {
-        const Tensor* T = &l->tt.t[kFirst[j]];
-        out[j] = qc_dqn_layer{base + T[0].off, base + T[1].off, kNoisy[j] ? nullptr : base + T[2].off,
-                              kNoisy[j] ? base + T[2].off : nullptr, kNoisy[j] ? base + T[3].off : nullptr};
-    }
+    layer_views(l, target ? l->PT : l->P, out);
     return QC_OK;
 }
 
 int qc_learner_grads(qc_learner* l, qc_dqn_layer out[6]) {
     if (!l || !out) return QC_EINVAL;
-    const float* base = l->G;
-    for (int j = 0; j < 6; ++j) {
-        const Tensor* T = &l->tt.t[kFirst[j]];
-        out[j] = qc_dqn_layer{base + T[0].off, base + T[1].off, kNoisy[j] ? nullptr : base + T[2].off,
-                              kNoisy[j] ? base + T[2].off : nullptr, kNoisy[j] ? base + T[3].off : nullptr};
-    }
+    layer_views(l, l->G, out);
     return QC_OK;
 }
 
@@ -920,7 +805,7 @@ int qc_learner_update(qc_learner* l, const float* transitions, const float* is_w
         hipError_t e = hipMemcpyAsync(l->PT, l->P, (size_t)l->np * sizeof(float), hipMemcpyDeviceToDevice, l->stream);
         if (e == hipSuccess)
             e = hipMemcpyAsync(l->FT, l->F, (size_t)l->nf_fwd * sizeof(float), hipMemcpyDeviceToDevice, l->stream);
-        if (e != hipSuccess) return hip_fail(l, e, "target network copy");
+        if (e != hipSuccess) return hip_fail(l->err, e, "target network copy");
         launches += 2;
     }
     l->backup_counter = (l->backup_counter + 1) % l->p.backup_period;
@@ -952,7 +837,7 @@ int qc_learner_update(qc_learner* l, const float* transitions, const float* is_w
     optimizer_and_prep(l, 1);
     launches += 8;
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(l, e, "learner update launch");
+    if (e != hipSuccess) return hip_fail(l->err, e, "learner update launch");
     l->updates += 1;
     l->launches = launches;
     return QC_OK;
@@ -981,10 +866,10 @@ int qc_learner_apply(qc_learner* l, const qc_dqn_layer grads[6]) {
         }
     }
     if (e == hipErrorInvalidValue) return QC_EINVAL;
-    if (e != hipSuccess) return hip_fail(l, e, "learner gradient copy");
+    if (e != hipSuccess) return hip_fail(l->err, e, "learner gradient copy");
     optimizer_and_prep(l, 0);
     e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(l, e, "learner optimizer launch");
+    if (e != hipSuccess) return hip_fail(l->err, e, "learner optimizer launch");
     return QC_OK;
 }
 
@@ -994,7 +879,7 @@ int qc_learner_stats(qc_learner* l, qc_learner_stats_t* out) {
     int32_t cnt[2] = {0, 0};
     hipError_t e = hipStreamSynchronize(l->stream);
     if (e == hipSuccess) e = hipMemcpy(cnt, l->d_cnt, sizeof(cnt), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail(l, e, "learner stats");
+    if (e != hipSuccess) return hip_fail(l->err, e, "learner stats");
     out->updates = l->updates;
     out->step = l->step;
     out->backup_counter = l->backup_counter;

@@ -25,6 +25,7 @@
 #include <string>
 
 #include "../../include/qcart.h"
+#include "qcart_host.hpp"
 #include "qcart_kernels.hpp"
 
 namespace qcart {
@@ -363,19 +364,8 @@ int rfail(qc_replay* r, int code, const std::string& msg) {
     return code;
 }
 
-struct Dev {
-    int prev = -1;
-    explicit Dev(int d) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != d) (void)hipSetDevice(d);
-    }
-    ~Dev() {
-        int cur = -1;
-        if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-    }
-};
-
-std::string g_replay_err;
+using qcart::host::Dev;
+qcart::host::CreateError g_replay_err;
 
 int grow(qc_replay* r, int64_t n) {
     if (n <= r->cap_n) return QC_OK;
@@ -453,23 +443,11 @@ extern "C" {
 int qc_replay_create(const qc_replay_params* p, int device, qc_replay** out) {
     if (!out) return QC_EINVAL;
     *out = nullptr;
-    if (!p || p->capacity < 1 || p->capacity > ((int64_t)1 << 30) || p->row_len < 1) {
-        g_replay_err = "capacity must be in [1, 2^30] and row_len >= 1";
-        return QC_EINVAL;
-    }
-    if (p->policy != 0 && p->policy != 1) {
-        g_replay_err = "policy must be 0 (sequential) or 1 (random)";
-        return QC_EINVAL;
-    }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        g_replay_err = "no HIP device available (libqcart has no CPU fallback)";
-        return QC_EHIP;
-    }
-    if (device < 0 || device >= ndev) {
-        g_replay_err = "device index out of range";
-        return QC_EINVAL;
-    }
+    if (!p || p->capacity < 1 || p->capacity > ((int64_t)1 << 30) || p->row_len < 1)
+        return g_replay_err.fail("capacity must be in [1, 2^30] and row_len >= 1", QC_EINVAL);
+    if (p->policy != 0 && p->policy != 1)
+        return g_replay_err.fail("policy must be 0 (sequential) or 1 (random)", QC_EINVAL);
+    if (const int rc = qcart::host::check_device(device, g_replay_err, "libqcart")) return rc;
     qc_replay* r = new qc_replay();
     r->p = *p;
     r->device = device;
@@ -490,9 +468,8 @@ int qc_replay_create(const qc_replay_params* p, int device, qc_replay** out) {
         hipMalloc((void**)&r->tree, (size_t)r->tree_size * sizeof(double)) != hipSuccess ||
         hipMalloc((void**)&r->data, data_bytes) != hipSuccess ||
         hipMalloc((void**)&r->owner, (size_t)p->capacity * sizeof(unsigned long long)) != hipSuccess) {
-        g_replay_err = "hipMalloc failed (capacity x row_len too large?)";
         qc_replay_destroy(r);
-        return QC_ENOMEM;
+        return g_replay_err.fail("hipMalloc failed (capacity x row_len too large?)", QC_ENOMEM);
     }
     State s{};
     s.passes = -p->passes_before_random;   // SumTree.passes = -passes_before_random (RL.py:260)
@@ -501,9 +478,8 @@ int qc_replay_create(const qc_replay_params* p, int device, qc_replay** out) {
     (void)hipMemset(r->data, 0, data_bytes);
     (void)hipMemset(r->owner, 0, (size_t)p->capacity * sizeof(unsigned long long));
     if (hipDeviceSynchronize() != hipSuccess) {
-        g_replay_err = "device initialisation failed";
         qc_replay_destroy(r);
-        return QC_EHIP;
+        return g_replay_err.fail("device initialisation failed", QC_EHIP);
     }
     *out = r;
     return QC_OK;
@@ -521,7 +497,7 @@ void qc_replay_destroy(qc_replay* r) {
     delete r;
 }
 
-const char* qc_replay_last_error(const qc_replay* r) { return r ? r->err.c_str() : g_replay_err.c_str(); }
+const char* qc_replay_last_error(const qc_replay* r) { return r ? r->err.c_str() : g_replay_err.text(); }
 
 int qc_replay_set_stream(qc_replay* r, void* stream) {
     if (!r) return QC_EINVAL;

@@ -36,8 +36,10 @@ def _shapes(data_length: int, n_actions: int):
     return ((512, data_length), (256, 512), (256, 256), (n_actions, 256), (128, 256), (1, 128))
 
 
-class DQNLearner:
+class DQNLearner(L.DeviceHandle):
     """TrainDQN for direct_DQN(data_length, noisy_layers=2) with LaProp(centered, betas (0.9, 0.9995))."""
+
+    _prefix = "qc_learner"
 
     def __init__(self, params: Mapping[str, torch.Tensor], batch_size: int = 512, gamma: float = 0.998,
                  lr: float = 4e-4, alive_reward: float = 10., failing_reward: float = -1., backup_period: int = 300,
@@ -64,7 +66,7 @@ class DQNLearner:
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             torch.cuda.init()
-            L.check_learner(L.lib().qc_learner_create(ctypes.byref(p), self.device.index, ctypes.byref(h)), None)
+            self._check(L.lib().qc_learner_create(ctypes.byref(p), self.device.index, ctypes.byref(h)))
         self._h = h
         self.noise_len = int(L.lib().qc_learner_noise_len(h))
         self.counter = 0
@@ -72,35 +74,17 @@ class DQNLearner:
         self._keep = []
         self.load_state_dict(params)
 
-    def close(self):
-        if getattr(self, "_h", None):
-            L.lib().qc_learner_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _bind_stream(self):
-        s = torch.cuda.current_stream(self.device).cuda_stream
-        L.check_learner(L.lib().qc_learner_set_stream(self._h, ctypes.c_void_p(s)), self._h)
-
     def _layer_array(self, params: Mapping[str, torch.Tensor]):
         layers = (L.QcDqnLayer * 6)()
         keep = []
         for i, (name, shape) in enumerate(zip(LAYERS, _shapes(self.data_length, self.n_actions))):
             if NOISY[i] != (f"{name}.u_w" in params):
                 raise ValueError(f"{name}: the learner covers direct_DQN(noisy_layers=2) only")
-            w, b, g, sw, sb = _layer_tensors(params, name, self.device)
-            if tuple(w.shape) != shape:
-                raise ValueError(f"{name}: weight shape {tuple(w.shape)} != {shape}")
-            keep += [w, b, g, sw, sb]
-            layers[i].weight, layers[i].bias = w.data_ptr(), b.data_ptr()
-            layers[i].weight_norm = g.data_ptr() if g is not None else None
-            layers[i].sigma_w = sw.data_ptr() if sw is not None else None
-            layers[i].sigma_b = sb.data_ptr() if sb is not None else None
+            t = _layer_tensors(params, name, self.device)
+            if tuple(t[0].shape) != shape:
+                raise ValueError(f"{name}: weight shape {tuple(t[0].shape)} != {shape}")
+            keep += t
+            L.fill_layer(layers[i], t)
         return layers, keep
 
     def load_state_dict(self, params: Mapping[str, torch.Tensor]):
@@ -109,7 +93,7 @@ class DQNLearner:
         layers, keep = self._layer_array(params)
         with torch.cuda.device(self.device):
             self._bind_stream()
-            L.check_learner(L.lib().qc_learner_load(self._h, layers), self._h)
+            self._check(L.lib().qc_learner_load(self._h, layers))
         self._keep = keep   # the copies read them on the current stream
 
     def _tensors(self, layers) -> dict:
@@ -130,14 +114,14 @@ class DQNLearner:
     def state_dict(self, target: bool = False) -> dict:
         """The online (or target) parameters under the reference's key names, as device copies."""
         layers = (L.QcDqnLayer * 6)()
-        L.check_learner(L.lib().qc_learner_layers(self._h, 1 if target else 0, layers), self._h)
+        self._check(L.lib().qc_learner_layers(self._h, 1 if target else 0, layers))
         with torch.cuda.device(self.device):
             return {k: v.clone() for k, v in self._tensors(layers).items()}
 
     def grads(self) -> dict:
         """Gradients of the last update under the parameters' key names (weight_norm: dg), as device copies."""
         layers = (L.QcDqnLayer * 6)()
-        L.check_learner(L.lib().qc_learner_grads(self._h, layers), self._h)
+        self._check(L.lib().qc_learner_grads(self._h, layers))
         with torch.cuda.device(self.device):
             return {k: v.clone() for k, v in self._tensors(layers).items()}
 
@@ -146,11 +130,11 @@ class DQNLearner:
         layers, keep = self._layer_array(grads)
         with torch.cuda.device(self.device):
             self._bind_stream()
-            L.check_learner(L.lib().qc_learner_apply(self._h, layers), self._h)
+            self._check(L.lib().qc_learner_apply(self._h, layers))
         self._keep = keep
 
     def set_lr(self, lr: float):
-        L.check_learner(L.lib().qc_learner_set_lr(self._h, float(lr)), self._h)
+        self._check(L.lib().qc_learner_set_lr(self._h, float(lr)))
 
     def update(self, transitions: torch.Tensor, is_weights: torch.Tensor, noise: Optional[torch.Tensor] = None,
                counter: Optional[int] = None) -> torch.Tensor:
@@ -176,9 +160,9 @@ class DQNLearner:
         vp = ctypes.c_void_p
         with torch.cuda.device(self.device):
             self._bind_stream()
-            L.check_learner(L.lib().qc_learner_update(
+            self._check(L.lib().qc_learner_update(
                 self._h, vp(tr.data_ptr()), vp(w.data_ptr()), vp(nz.data_ptr()) if nz is not None else None,
-                int(counter), vp(ul.data_ptr()), vp(self.last_loss.data_ptr())), self._h)
+                int(counter), vp(ul.data_ptr()), vp(self.last_loss.data_ptr())))
         return ul
 
     def step(self, memory, counter: Optional[int] = None):
@@ -195,7 +179,7 @@ class DQNLearner:
     def push(self, actor):
         """Load the online fc1, fc2, fc31, fc41 into a DQNActor, device to device (no host copy)."""
         layers = (L.QcDqnLayer * 6)()
-        L.check_learner(L.lib().qc_learner_layers(self._h, 0, layers), self._h)
+        self._check(L.lib().qc_learner_layers(self._h, 0, layers))
         with torch.cuda.device(self.device):
             actor._bind_stream()
             L.check_actor(L.lib().qc_actor_load(actor._h, layers), actor._h)
@@ -203,6 +187,5 @@ class DQNLearner:
     def stats(self) -> dict:
         """Synchronises. Raises QCartError if an update since the last call saw an out-of-range action."""
         s = L.QcLearnerStats()
-        rc = L.lib().qc_learner_stats(self._h, ctypes.byref(s))
-        L.check_learner(rc, self._h)
+        self._check(L.lib().qc_learner_stats(self._h, ctypes.byref(s)))
         return {k: getattr(s, k) for k, _ in L.QcLearnerStats._fields_}

@@ -17,8 +17,10 @@ def _ptr(t: Optional[torch.Tensor]):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
 
-class PrioritizedReplay:
+class PrioritizedReplay(L.DeviceHandle):
     """Memory(capacity, data_size, policy, passes_before_random) (RL.py:377-386) on `device`."""
+
+    _prefix = "qc_replay"
 
     alpha = 0.2
     beta = 0.2
@@ -53,21 +55,6 @@ class PrioritizedReplay:
         self._h = h
         self._len_ok = 0   # largest n for which len(memory) >= n has been seen
 
-    def close(self):
-        if getattr(self, "_h", None):
-            L.lib().qc_replay_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _bind(self):
-        s = torch.cuda.current_stream(self.device).cuda_stream
-        L.check_replay(L.lib().qc_replay_set_stream(self._h, ctypes.c_void_p(s)), self._h)
-
     def _dev(self, t, dtype):
         return t.to(device=self.device, dtype=dtype).contiguous() if t is not None else None
 
@@ -78,7 +65,7 @@ class PrioritizedReplay:
         if rows.dim() != 2 or rows.shape[1] != self.data_size:
             raise ValueError(f"rows must be (n, {self.data_size})")
         valid = self._dev(valid, torch.uint8)
-        self._bind()
+        self._bind_stream()
         L.check_replay(L.lib().qc_replay_store(self._h, rows.shape[0], _ptr(valid), _ptr(rows)), self._h)
 
     def store_xp(self, last_obs: torch.Tensor, obs: torch.Tensor, action: torch.Tensor, reward: torch.Tensor,
@@ -88,7 +75,7 @@ class PrioritizedReplay:
         action, reward = self._dev(action, torch.int32), self._dev(reward, torch.float32)
         valid = self._dev(valid, torch.uint8)
         n, d = obs.shape
-        self._bind()
+        self._bind_stream()
         L.check_replay(L.lib().qc_replay_store_xp(self._h, n, _ptr(valid), _ptr(last_obs), _ptr(obs), d,
                                                   _ptr(action), _ptr(reward)), self._h)
 
@@ -105,7 +92,7 @@ class PrioritizedReplay:
         idx = torch.empty((n,), dtype=torch.int32, device=self.device)
         w = torch.empty((n,), dtype=torch.float32, device=self.device)
         u = self._dev(u, torch.float64)
-        self._bind()
+        self._bind_stream()
         L.check_replay(L.lib().qc_replay_sample(self._h, int(n), _ptr(u), _ptr(transitions), _ptr(idx), _ptr(w)),
                        self._h)
         return idx, w, transitions
@@ -113,12 +100,12 @@ class PrioritizedReplay:
     def batch_update(self, tree_idx: torch.Tensor, abs_errors: torch.Tensor):
         tree_idx = self._dev(tree_idx, torch.int32)
         abs_errors = self._dev(abs_errors, torch.float32)
-        self._bind()
+        self._bind_stream()
         L.check_replay(L.lib().qc_replay_update(self._h, tree_idx.numel(), _ptr(tree_idx), _ptr(abs_errors)),
                        self._h)
 
     def clean(self):
-        self._bind()
+        self._bind_stream()
         L.check_replay(L.lib().qc_replay_rebuild(self._h), self._h)
 
     def stats(self) -> dict:
