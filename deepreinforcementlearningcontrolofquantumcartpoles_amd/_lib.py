@@ -105,6 +105,7 @@ class QcDqnParams(ctypes.Structure):
         ("n_actions", ctypes.c_int32),
         ("max_batch", ctypes.c_int64),
         ("seed", ctypes.c_uint64),
+        ("hidden2", ctypes.c_int32),
     ]
 
 
@@ -139,7 +140,14 @@ class QcLearnerParams(ctypes.Structure):
         ("alive_reward", ctypes.c_double),
         ("failing_reward", ctypes.c_double),
         ("seed", ctypes.c_uint64),
+        ("hidden2", ctypes.c_int32),
+        ("target_mode", ctypes.c_int32),
+        ("beta1", ctypes.c_double),
+        ("beta2", ctypes.c_double),
     ]
+
+
+TD_TARGETS = {"alive": 0, "reward_fail": 1, "reward": 2}   # QC_TD_ALIVE, QC_TD_REWARD_FAIL, QC_TD_REWARD
 
 
 class QcLearnerStats(ctypes.Structure):

@@ -26,6 +26,15 @@ from . import _lib as L
 
 LAYERS = ("fc1", "fc2", "fc31", "fc41")
 HIDDEN = (512, 256, 256)
+HIDDEN2 = (256, 512)   # fc2's width: the harmonic / inverted harmonic net, the quartic / inverted quartic net
+
+
+def fc2_width(params: Mapping[str, torch.Tensor], hidden2: Optional[int]) -> int:
+    """fc2's width of a handle: `hidden2`, or (None) the parameters' own."""
+    w = int(params["fc2.weight"].shape[0]) if hidden2 is None else int(hidden2)
+    if w not in HIDDEN2:
+        raise ValueError(f"hidden2 must be 256 or 512 (fc2's width), not {w}")
+    return w
 
 
 def _layer_tensors(params: Mapping[str, torch.Tensor], name: str, dev: torch.device):
@@ -101,15 +110,19 @@ class _ActorHandle(L.DeviceHandle):
 
 
 class DQNActor(_ActorHandle):
-    """Device-side action selection for B envs with a reference direct_DQN's parameters."""
+    """Device-side action selection for B envs with a reference direct_DQN's parameters. hidden2: fc2's width,
+    256 (the harmonic and inverted harmonic drivers' net) or 512 (the quartic and inverted quartic drivers');
+    None takes it from `fc2.weight`. It is fixed for the handle's life: `load` refuses the other net."""
 
     _prefix = "qc_actor"
 
     def __init__(self, params: Mapping[str, torch.Tensor], data_length: int = 5, n_actions: int = 21,
-                 max_batch: int = 65536, device: int | str | torch.device = 0, seed: int = 0):
+                 max_batch: int = 65536, device: int | str | torch.device = 0, seed: int = 0,
+                 hidden2: Optional[int] = None):
         self.data_length = int(data_length)
+        self.hidden2 = fc2_width(params, hidden2)
         p = L.QcDqnParams()
-        p.data_length, p.seed = self.data_length, int(seed)
+        p.data_length, p.seed, p.hidden2 = self.data_length, int(seed), self.hidden2
         self._create(p, device, n_actions, max_batch)
         self.load(params)
 
@@ -118,10 +131,11 @@ class DQNActor(_ActorHandle):
         main_parallel.py:400-405). Noisy / weight-normalised layers are recognised by their keys."""
         layers = (L.QcDqnLayer * 4)()
         keep = []
+        hidden = (HIDDEN[0], self.hidden2, HIDDEN[2])
         for i, name in enumerate(LAYERS):
             t = _layer_tensors(params, name, self.device)
-            out_f = HIDDEN[i] if i < 3 else self.n_actions
-            in_f = self.data_length if i == 0 else HIDDEN[i - 1]
+            out_f = hidden[i] if i < 3 else self.n_actions
+            in_f = self.data_length if i == 0 else hidden[i - 1]
             if tuple(t[0].shape) != (out_f, in_f):
                 raise ValueError(f"{name}: weight shape {tuple(t[0].shape)} != {(out_f, in_f)}")
             keep += t
@@ -140,12 +154,16 @@ class DQNActor(_ActorHandle):
 
 
 def random_direct_dqn(data_length: int = 5, n_actions: int = 21, noisy_layers: int = 2, seed: int = 0,
-                      device: str | torch.device = "cpu") -> dict:
+                      device: str | torch.device = "cpu", hidden2: int = 256) -> dict:
     """Random-initialised parameters of the reference direct_DQN (RL.py:80-111) as a state_dict, with
     the reference's initialisers: nn.Linear's default for Linear_weight_normalize (weight_norm = the
     initial ||W||_F, layers.py:97-100) and FactorizedNoisy's kaiming-uniform u_w, zero u_b and
-    sigma = 0.5 / sqrt(in) (layers.py:22-29). Synthetic weights for tests and benchmarks."""
+    sigma = 0.5 / sqrt(in) (layers.py:22-29). hidden2 = 512 gives the quartic drivers' net (fc2 512 -> 512,
+    fc31 512 -> 256, fc32 512 -> 128). Synthetic weights for tests and benchmarks."""
+    if hidden2 not in HIDDEN2:
+        raise ValueError(f"hidden2 must be 256 or 512 (fc2's width), not {hidden2}")
     g = torch.Generator().manual_seed(seed)
+    h2 = int(hidden2)
 
     def linear(name, i, o):
         bound = 1.0 / math.sqrt(i)
@@ -162,9 +180,9 @@ def random_direct_dqn(data_length: int = 5, n_actions: int = 21, noisy_layers: i
 
     p = {}
     p.update(linear("fc1", data_length, 512))
-    p.update(linear("fc2", 512, 256))
-    p.update(noisy("fc31", 256, 256) if noisy_layers >= 2 else linear("fc31", 256, 256))
-    p.update(linear("fc32", 256, 128))
+    p.update(linear("fc2", 512, h2))
+    p.update(noisy("fc31", h2, 256) if noisy_layers >= 2 else linear("fc31", h2, 256))
+    p.update(linear("fc32", h2, 128))
     p.update(noisy("fc41", 256, n_actions) if noisy_layers >= 1 else linear("fc41", 256, n_actions))
     p.update(linear("fc42", 128, 1))
     return {k: v.to(device=device, dtype=torch.float32) for k, v in p.items()}

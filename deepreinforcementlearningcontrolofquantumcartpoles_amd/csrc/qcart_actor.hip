@@ -51,10 +51,15 @@ __device__ __forceinline__ float noise_at(const ActArgs& a, int f, int64_t e) {
     return a.noise[(int64_t)f * a.noise_ld + e];
 }
 
+// W2: fc2's width (qcart_dqn.hpp). The measurement network's tail (h_in) exists at W2 = 256 only
+template <int W2>
 __global__ __launch_bounds__(kThreads) void k_actor_act(const ActArgs a) {
+    constexpr int kEpsIn31 = NoiseAt<W2>::kEpsIn31, kEpsOut31 = NoiseAt<W2>::kEpsOut31,
+                  kEpsIn41 = NoiseAt<W2>::kEpsIn41, kEpsOut41 = NoiseAt<W2>::kEpsOut41;
+    constexpr bool kWide = W2 != kH2;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* RA = lds;                      // H1 [512][32]; later H3 [256][32] + H3e [256][32]
-    float* RB = lds + kH1 * kE;           // X0 [in_pad][32]; later H2 [256][32] + H2e [256][32]
+    float* RB = lds + kH1 * kE;           // X0 [in_pad][32]; later H2 [256][32] + H2e [256][32], or H2 [512][32]
     float* RC = lds + 2 * kH1 * kE;       // fc41 sigma partial
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t e0 = (int64_t)blockIdx.x * kE;
@@ -63,9 +68,9 @@ __global__ __launch_bounds__(kThreads) void k_actor_act(const ActArgs a) {
     const bool env_ok = eg < a.B;
 
     float* H2 = RB;
-    float* H2e = RB + kH2 * kE;
+    float* H2e = kWide ? RA : RB + kH2 * kE;   // wide: over H1, once fc2 is complete
     const bool n31 = a.noisy && a.L[2].s != nullptr;
-    if (a.h_in) {
+    if (!kWide && a.h_in) {
         // DQN_measurement: relu(fc1(x)) from HBM (coalesced 32-env rows) -> H2, eps_in(fc21) o H2
         for (int i = tid; i < kH2 * kE; i += kThreads) {
             const int k = i / kE, e = i % kE;
@@ -88,25 +93,46 @@ __global__ __launch_bounds__(kThreads) void k_actor_act(const ActArgs a) {
         });
         __syncthreads();
         // ---- fc2: ReLU; also eps_in(fc31) o H2 for the noisy GEMM
-        dense4(a.L[1].u, nullptr, RA, nullptr, kH2, kH1, lane, wave, [&](int o, float y, float) {
+        dense4(a.L[1].u, nullptr, RA, nullptr, W2, kH1, lane, wave, [&](int o, float y, float) {
             const float h = fmaxf(y + a.L[1].ub[o], 0.f);
             H2[o * kE + env] = h;
-            if (n31) H2e[o * kE + env] = env_ok ? h * noise_at(a, kEpsIn31 + o, eg) : 0.f;
+            if (!kWide && n31) H2e[o * kE + env] = env_ok ? h * noise_at(a, kEpsIn31 + o, eg) : 0.f;
         });
         __syncthreads();
+        if (kWide && n31) {
+            for (int i = tid; i < W2 * kE; i += kThreads) {
+                const int k = i / kE, e = i % kE;
+                H2e[i] = e0 + e < a.B ? H2[i] * noise_at(a, kEpsIn31 + k, e0 + e) : 0.f;
+            }
+            __syncthreads();
+        }
     }
 
     // ---- fc31 (noisy or weight-normalised): ReLU; eps_in(fc41) o H3
     float* H3 = RA;
     float* H3e = RA + kH3 * kE;
     const bool n41 = a.noisy && a.L[3].s != nullptr;
-    dense4(a.L[2].u, n31 ? a.L[2].s : nullptr, H2, H2e, kH3, kH2, lane, wave, [&](int o, float yu, float ys) {
+    auto act31 = [&](int o, float yu, float ys) {
         float y = yu + a.L[2].ub[o];
         if (n31) y += env_ok ? noise_at(a, kEpsOut31 + o, eg) * (ys + a.L[2].sb[o]) : 0.f;
-        const float h = fmaxf(y, 0.f);
+        return fmaxf(y, 0.f);
+    };
+    auto put3 = [&](int o, float h) {
         H3[o * kE + env] = h;
         if (n41) H3e[o * kE + env] = env_ok ? h * noise_at(a, kEpsIn41 + o, eg) : 0.f;
-    });
+    };
+    if constexpr (kWide) {
+        float hold[2][16];
+        dense4_hold2(a.L[2].u, n31 ? a.L[2].s : nullptr, H2, H2e, W2, lane, wave, hold, act31);
+        __syncthreads();   // every wave is done reading H2 / H2e: RA is free
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) put3((wave + 4 * j) * 32 + drow(r, lane), hold[j][r]);
+    } else {
+        dense4(a.L[2].u, n31 ? a.L[2].s : nullptr, H2, H2e, kH3, W2, lane, wave,
+               [&](int o, float yu, float ys) { put3(o, act31(o, yu, ys)); });
+    }
     __syncthreads();
 
     // ---- fc41 -> action values, argmax (lowest index among equal maxima)
@@ -464,6 +490,7 @@ struct ActorCore {
     std::string err;
     bool loaded = false;
     int n_act = 0, noise_len = 0;
+    int w2 = kH2;                // fc2's width (k_actor_act's instantiation); the measurement actor's tail: 256
     int64_t max_batch = 0;       // also the noise buffer's leading dimension
     uint64_t seed = 0;
     float* d_w = nullptr;        // all fragments + padded biases
@@ -495,9 +522,9 @@ constexpr LayerRule kMactorRules[] = {
      "fc21 / fc31: FactorizedNoisy or Linear_weight_normalize"},
 };
 
-bool enable_act_lds() {
-    return hipFuncSetAttribute((const void*)k_actor_act, hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)kActLdsBytes) == hipSuccess;
+bool enable_act_lds(int w2) {
+    const void* f = w2 == kH2Wide ? (const void*)k_actor_act<kH2Wide> : (const void*)k_actor_act<kH2>;
+    return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kActLdsBytes) == hipSuccess;
 }
 
 // the end of an act call: the noise (injected and transposed, or drawn), then k_actor_act; k holds the input side
@@ -528,7 +555,11 @@ int act_tail(ActorCore* a, ActArgs& k, const char* what, int64_t B, int64_t env_
     k.actions = actions;
     k.q_out = q_out;
     k.random_out = random_out;
-    hipLaunchKernelGGL(k_actor_act, dim3((unsigned)((B + kE - 1) / kE)), dim3(kThreads), kActLdsBytes, a->stream, k);
+    const dim3 grid((unsigned)((B + kE - 1) / kE));
+    if (a->w2 == kH2Wide)
+        hipLaunchKernelGGL(k_actor_act<kH2Wide>, grid, dim3(kThreads), kActLdsBytes, a->stream, k);
+    else
+        hipLaunchKernelGGL(k_actor_act<kH2>, grid, dim3(kThreads), kActLdsBytes, a->stream, k);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(a->err, e, what);
     return QC_OK;
@@ -542,6 +573,8 @@ int qc_actor_create(const qc_dqn_params* p, int device, qc_actor** out) {
     *out = nullptr;
     if (const char* m = bad_net_size(p->data_length, p->n_actions)) return g_actor_err.fail(m, QC_EINVAL);
     if (p->max_batch < 1) return g_actor_err.fail("max_batch must be >= 1", QC_EINVAL);
+    const int w2 = fc2_width(p->hidden2);
+    if (!w2) return g_actor_err.fail("hidden2 must be 0, 256 or 512 (fc2's width)", QC_EINVAL);
     if (const int rc = check_device(device, g_actor_err, "the actor")) return rc;
     qc_actor* a = new qc_actor();
     a->p = *p;
@@ -550,9 +583,10 @@ int qc_actor_create(const qc_dqn_params* p, int device, qc_actor** out) {
     a->max_batch = p->max_batch;
     a->seed = p->seed;
     a->in_pad = in_pad(p->data_length);
-    a->noise_len = noise_len(p->n_actions);
-    const int K[4] = {a->in_pad, kH1, kH2, kH3};
-    const int O[4] = {kH1, kH2, kH3, p->n_actions};
+    a->w2 = w2;
+    a->noise_len = noise_len(w2, p->n_actions);
+    const int K[4] = {a->in_pad, kH1, w2, kH3};
+    const int O[4] = {kH1, w2, kH3, p->n_actions};
     // fc31 / fc41 may be loaded either way; fc1 / fc2 never use their sigma regions, but without them fc2's
     // fragments start off a 4 KiB boundary and k_actor_act measures 1.3 % slower (65 536 envs)
     const bool noisy[4] = {true, true, true, true};
@@ -561,7 +595,7 @@ int qc_actor_create(const qc_dqn_params* p, int device, qc_actor** out) {
     hipError_t e = hipMalloc(&a->d_w, floats * sizeof(float));
     if (e == hipSuccess) e = hipMemset(a->d_w, 0, floats * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(&a->d_noise, (size_t)a->noise_len * (size_t)p->max_batch * sizeof(float));
-    const bool lds_ok = e == hipSuccess && enable_act_lds();
+    const bool lds_ok = e == hipSuccess && enable_act_lds(w2);
     if (!lds_ok) {
         if (a->d_w) (void)hipFree(a->d_w);
         if (a->d_noise) (void)hipFree(a->d_noise);
@@ -597,9 +631,9 @@ int qc_actor_noise_len(const qc_actor* a) { return a ? a->noise_len : QC_EINVAL;
 int qc_actor_load(qc_actor* a, const qc_dqn_layer layers[4]) {
     if (!a || !layers) return QC_EINVAL;
     if (const int rc = validate_layers(layers, 4, kActorRules, 4, a->err)) return rc;
-    const int K[4] = {a->p.data_length, kH1, kH2, kH3};
-    const int Kp[4] = {a->in_pad, kH1, kH2, kH3};
-    const int O[4] = {kH1, kH2, kH3, a->p.n_actions};
+    const int K[4] = {a->p.data_length, kH1, a->w2, kH3};
+    const int Kp[4] = {a->in_pad, kH1, a->w2, kH3};
+    const int O[4] = {kH1, a->w2, kH3, a->p.n_actions};
     Dev g(a->device);
     float* w = a->d_w;
     for (int l = 0; l < 4; ++l) {
@@ -670,7 +704,7 @@ int qc_mactor_create(const qc_mdqn_params* p, int device, qc_mactor** out) {
     a->seed = p->seed;
     a->T1 = T1; a->T2 = T2; a->T3 = T3;
     a->flat = kC3 * T3;
-    a->noise_len = noise_len(p->n_actions);
+    a->noise_len = noise_len(kH2, p->n_actions);
     a->chunk = (int)std::min<int64_t>(p->max_batch, p->chunk > 0 ? p->chunk : 2048);
     const int O[6] = {kC1, kC2, kC3, kH2, kH3, p->n_actions};
     const int K[6] = {2 * 13, kC1 * 11, kC2 * 9, a->flat, kH2, kH3};
@@ -686,7 +720,7 @@ int qc_mactor_create(const qc_mdqn_params* p, int device, qc_mactor** out) {
     if (e == hipSuccess) e = hipMalloc(&a->d_y3, (size_t)a->flat * mb * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(&a->d_h1, (size_t)kH2 * mb * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(&a->d_noise, (size_t)a->noise_len * mb * sizeof(float));
-    if (e != hipSuccess || !enable_act_lds()) {
+    if (e != hipSuccess || !enable_act_lds(kH2)) {
         qc_mactor_destroy(a);
         return g_mactor_err.fail("device allocation failed", QC_ENOMEM);
     }

@@ -17,6 +17,11 @@ namespace dqn {
 using namespace qcart::mfma;   // kE, f32x16, tiles / ksteps, gemm_tile, drow
 
 constexpr int kH1 = 512, kH2 = 256, kH3 = 256, kHM = 128;   // fc1, fc2, fc31, fc32 widths
+// fc2's width is the one that differs between the reference's drivers: 256 (harmonic, inverted harmonic: kH2)
+// or 512 (quartic, inverted quartic: kH2Wide); the kernels take it as a template argument W2
+constexpr int kH2Wide = 512;
+// a params struct's hidden2 field -> the width (0: the narrow net), or 0 where it is neither
+inline int fc2_width(int hidden2) { return hidden2 == 0 || hidden2 == kH2 ? kH2 : hidden2 == kH2Wide ? kH2Wide : 0; }
 constexpr int kMaxIn = 512;      // data_length limit (LDS: [in][32] fp32 within 64 KiB)
 constexpr int kThreads = 256;    // 4 waves
 __host__ __device__ constexpr int in_pad(int data_length) { return (data_length + 1) & ~1; }
@@ -28,12 +33,18 @@ inline const char* bad_net_size(int data_length, int n_actions) {
     return nullptr;
 }
 
-// one noise sample, as FactorizedNoisy draws it: eps_in / eps_out of fc31, then of fc41 (n_actions long)
-constexpr int kEpsIn31 = 0, kEpsOut31 = kEpsIn31 + kH2, kEpsIn41 = kEpsOut31 + kH3, kEpsOut41 = kEpsIn41 + kH3;
-__host__ __device__ constexpr int noise_len(int n_actions) { return kEpsOut41 + n_actions; }
+// one noise sample, as FactorizedNoisy draws it: eps_in [W2] / eps_out [256] of fc31, then eps_in [256] /
+// eps_out [n_actions] of fc41
+template <int W2>
+struct NoiseAt {
+    static constexpr int kEpsIn31 = 0, kEpsOut31 = kEpsIn31 + W2, kEpsIn41 = kEpsOut31 + kH3, kEpsOut41 = kEpsIn41 + kH3;
+};
+__host__ __device__ constexpr int noise_len(int w2, int n_actions) { return w2 + 2 * kH3 + n_actions; }
 
 // k_actor_act's LDS: RA = H1 [512][32], later H3 + eps_in o H3; RB = X0 [in_pad][32], later H2 + eps_in o H2;
-// RC = fc41's sigma partial as D registers [16][64]
+// RC = fc41's sigma partial as D registers [16][64]. At W2 = 512 H2 fills RB, so eps_in o H2 goes over the
+// dead H1 in RA, fc31's output waits in registers (dense4_hold2) until both are dead, and H3 + eps_in o H3
+// then go to RA: the same two 64 KiB regions, two barriers more
 constexpr int kActLdsFloats = 2 * kH1 * kE + 16 * 64;
 constexpr size_t kActLdsBytes = kActLdsFloats * sizeof(float);
 
@@ -50,6 +61,26 @@ __device__ __forceinline__ void dense4(const float* __restrict__ uf, const float
         if (sf) gemm_tile(accs, sf + (size_t)t * S * 64, xe, S, lane);
 #pragma unroll
         for (int r = 0; r < 16; ++r) epi(t * 32 + drow(r, lane), acc[r], accs[r]);
+    }
+}
+
+// A 256-output layer whose results cannot go to LDS yet (its operands fill both regions): wave w computes
+// tiles w and w + 4 as dense4 does and keeps hold[j][r] = epi(o, y_u, y_sigma) for tile w + 4 j, D element r
+// (output o = (w + 4 j) 32 + drow(r, lane)); the caller stores them after its next barrier
+template <class Epi>
+__device__ __forceinline__ void dense4_hold2(const float* __restrict__ uf, const float* __restrict__ sf, const float* x,
+                                             const float* xe, int K, int lane, int wave, float (&hold)[2][16],
+                                             Epi epi) {
+    static_assert(tiles(kH3) == 8, "two tiles for each of the 4 waves");
+    const int S = ksteps(K);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int t = wave + 4 * j;
+        f32x16 acc = {}, accs = {};
+        gemm_tile(acc, uf + (size_t)t * S * 64, x, S, lane);
+        if (sf) gemm_tile(accs, sf + (size_t)t * S * 64, xe, S, lane);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) hold[j][r] = epi(t * 32 + drow(r, lane), acc[r], accs[r]);
     }
 }
 

@@ -1,6 +1,8 @@
 // qcart_learner.hip — the device DQN learner: the reference's TrainDQN.__call__ (inverted harmonic
 // oscillator/RL.py:159-232) with its LaProp optimizer (optimizer.py) for the 'xp' network direct_DQN
 // (RL.py:80-106, layers.py), one update per call on a batch of B transitions, fp32 throughout.
+// The four drivers' RL.py differ in fc2's width (256 / 512: the W2 template argument of k_learner_fwd / k_learner_bwd),
+// in the TD target (k_learner_loss's mode, QC_TD_*) and in LaProp's betas: all three are handle parameters.
 //
 // Launches per update (plain launches on the handle's stream, no atomics on any gradient, so the same
 // inputs give bit-identical parameters):
@@ -58,10 +60,16 @@ struct LArgs {
 
 __device__ __forceinline__ float nz(const LArgs& a, int f, int row) { return a.noise[f * kChunks + row / a.rpc]; }
 
+// W2: fc2's width. At W2 = 512 the LDS plan is the wide actor's (qcart_dqn.hpp): eps_in o H2 over the dead H1,
+// fc31's output held in registers across one barrier; fc32 reads H2 before that barrier
+template <int W2>
 __global__ __launch_bounds__(kThreads) void k_learner_fwd(const LArgs a) {
+    constexpr int kEpsIn31 = NoiseAt<W2>::kEpsIn31, kEpsOut31 = NoiseAt<W2>::kEpsOut31,
+                  kEpsIn41 = NoiseAt<W2>::kEpsIn41, kEpsOut41 = NoiseAt<W2>::kEpsOut41;
+    constexpr bool kWide = W2 != kH2;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* RA = lds;                      // H1 [512][32]; later H3 [256][32] + H3e [256][32]
-    float* RB = lds + kH1 * kE;           // X0 [in_pad][32]; later H2 [256][32] + H2e [256][32]
+    float* RB = lds + kH1 * kE;           // X0 [in_pad][32]; later H2 [256][32] + H2e [256][32], or H2 [512][32]
     float* RC = lds + 2 * kH1 * kE;       // fc41 sigma partial, as D registers
     float* RD = RC + 16 * 64;             // R32 [128][32]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -91,25 +99,41 @@ __global__ __launch_bounds__(kThreads) void k_learner_fwd(const LArgs a) {
 
     // ---- fc2: ReLU; eps_in(fc31) o H2
     float* H2 = RB;
-    float* H2e = RB + kH2 * kE;
-    dense4(F + a.fo.u[1], nullptr, RA, nullptr, kH2, kH1, lane, wave, [&](int o, float y, float) {
+    float* H2e = kWide ? RA : RB + kH2 * kE;   // wide: over H1, once fc2 is complete
+    dense4(F + a.fo.u[1], nullptr, RA, nullptr, W2, kH1, lane, wave, [&](int o, float y, float) {
         const float h = fmaxf(y + F[a.fo.ub[1] + o], 0.f);
-        const float he = h * nz(a, kEpsIn31 + o, eg);
-        H2[o * kE + env] = h;
-        H2e[o * kE + env] = he;
-        if (ws) {
-            a.H2[(size_t)o * B + eg] = h;
-            a.H2e[(size_t)o * B + eg] = he;
+        if constexpr (kWide) {
+            H2[o * kE + env] = h;
+            if (ws) a.H2[(size_t)o * B + eg] = h;
+        } else {
+            const float he = h * nz(a, kEpsIn31 + o, eg);
+            H2[o * kE + env] = h;
+            H2e[o * kE + env] = he;
+            if (ws) {
+                a.H2[(size_t)o * B + eg] = h;
+                a.H2e[(size_t)o * B + eg] = he;
+            }
         }
     });
     __syncthreads();
+    if constexpr (kWide) {
+        for (int i = tid; i < W2 * kE; i += kThreads) {
+            const int k = i / kE, e = i % kE;
+            const float he = H2[i] * nz(a, kEpsIn31 + k, e0 + e);
+            H2e[i] = he;
+            if (ws) a.H2e[(size_t)k * B + e0 + e] = he;
+        }
+        __syncthreads();
+    }
 
     // ---- fc31 (noisy): ReLU; eps_in(fc41) o H3
     float* H3 = RA;
     float* H3e = RA + kH3 * kE;
-    dense4(F + a.fo.u[2], F + a.fo.s[2], H2, H2e, kH3, kH2, lane, wave, [&](int o, float yu, float ys) {
+    auto act31 = [&](int o, float yu, float ys) {
         const float y = yu + F[a.fo.ub[2] + o] + nz(a, kEpsOut31 + o, eg) * (ys + F[a.fo.sb[2] + o]);
-        const float h = fmaxf(y, 0.f);
+        return fmaxf(y, 0.f);
+    };
+    auto put3 = [&](int o, float h) {
         const float he = h * nz(a, kEpsIn41 + o, eg);
         H3[o * kE + env] = h;
         H3e[o * kE + env] = he;
@@ -117,15 +141,28 @@ __global__ __launch_bounds__(kThreads) void k_learner_fwd(const LArgs a) {
             a.A3[(size_t)o * B + eg] = h;
             a.A3e[(size_t)o * B + eg] = he;
         }
-    });
+    };
+    float hold[kWide ? 2 : 1][16];
+    if constexpr (kWide)
+        dense4_hold2(F + a.fo.u[2], F + a.fo.s[2], H2, H2e, W2, lane, wave, hold, act31);
+    else
+        dense4(F + a.fo.u[2], F + a.fo.s[2], H2, H2e, kH3, W2, lane, wave,
+               [&](int o, float yu, float ys) { put3(o, act31(o, yu, ys)); });
     // ---- fc32 (mean head): 4 tiles, 1 per wave; ReLU (the next-state argmax pass needs no mean)
     if (pass != 0)
-        dense4(F + a.fo.u[4], nullptr, H2, nullptr, kHM, kH2, lane, wave, [&](int o, float y, float) {
+        dense4(F + a.fo.u[4], nullptr, H2, nullptr, kHM, W2, lane, wave, [&](int o, float y, float) {
             const float h = fmaxf(y + F[a.fo.ub[4] + o], 0.f);
             RD[o * kE + env] = h;
             if (ws) a.R32[(size_t)o * B + eg] = h;
         });
     __syncthreads();
+    if constexpr (kWide) {   // every wave is done reading H2 / H2e: RA is free
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) put3((wave + 4 * j) * 32 + drow(r, lane), hold[j][r]);
+        __syncthreads();
+    }
 
     // ---- fc41 -> Q; beside it fc42 on wave 2 (row 0 of its tile) -> M
     fc41(F + a.fo.u[3], F + a.fo.s[3], H3, H3e, RC, a.n_act, lane, wave,
@@ -148,13 +185,16 @@ struct LossArgs {
     const float* w;
     const float* noise;
     int B, n_act, in_len, row_len, rpc;
-    float gamma, rew, failing, inv_B, inv_A;
+    int eps_out41;   // NoiseAt<W2>::kEpsOut41 of the handle's net
+    float gamma, rew /* (1 - gamma) alive_reward */, omg /* 1 - gamma */, failing, inv_B, inv_A;
     float *dQ, *dQe, *dM, *ul, *loss, *loss_user;
     int32_t* cnt;   // [0] non-finite losses, [1] rows with an action outside [0, n_act)
 };
 
 // argmax of Q_online(next) (first index among equal maxima), the two gathers, the TD target, ul, the loss
-// mean and the head gradients dQ [32][B] (rows >= n_act exact zeros), eps_out(fc41) o dQ, dm [B]
+// mean and the head gradients dQ [32][B] (rows >= n_act exact zeros), eps_out(fc41) o dQ, dm [B]. MODE: the TD
+// target, QC_TD_ALIVE / QC_TD_REWARD_FAIL / QC_TD_REWARD (include/qcart.h)
+template <int MODE>
 __global__ __launch_bounds__(1024) void k_learner_loss(const LossArgs a) {
     __shared__ float part[1024];
     float lsum = 0.f;
@@ -180,8 +220,15 @@ __global__ __launch_bounds__(1024) void k_learner_loss(const LossArgs a) {
         }
         const float sav = q1[act] + a.M[a.B + b] - s1 * a.inv_A;
         const float nsv = q2[best] + a.M[2 * a.B + b] - s2 * a.inv_A;
-        float y = nsv * a.gamma + a.rew;
-        if (row[2 * a.in_len + 1] == a.failing) y = 0.f;
+        float y;
+        if constexpr (MODE == QC_TD_ALIVE) {   // IHO / IQO RL.py: the alive reward, 0 on a failing row
+            y = nsv * a.gamma + a.rew;
+            if (row[2 * a.in_len + 1] == a.failing) y = 0.f;
+        } else {                               // QO / HO RL.py: the row's own reward
+            const float r = row[2 * a.in_len + 1];
+            y = nsv * a.gamma + a.omg * r;
+            if (MODE == QC_TD_REWARD_FAIL && r <= a.failing) y = r;
+        }
         const float d = sav - y;
         const float ul = d * d;
         a.ul[b] = ul;
@@ -192,7 +239,7 @@ __global__ __launch_bounds__(1024) void k_learner_loss(const LossArgs a) {
         for (int j = 0; j < 32; ++j) {
             const float g = j < a.n_act ? delta * ((j == act ? 1.f : 0.f) - a.inv_A) : 0.f;
             a.dQ[(size_t)j * a.B + b] = g;
-            a.dQe[(size_t)j * a.B + b] = j < a.n_act ? g * a.noise[(kEpsOut41 + j) * kChunks + c] : 0.f;
+            a.dQe[(size_t)j * a.B + b] = j < a.n_act ? g * a.noise[(a.eps_out41 + j) * kChunks + c] : 0.f;
         }
     }
     lsum = block_sum(lsum, part);
@@ -204,9 +251,13 @@ __global__ __launch_bounds__(1024) void k_learner_loss(const LossArgs a) {
     }
 }
 
-// dX down the online net for 32 rows: LDS holds dQ / dQe [32][32], dZ3 / dZ3e [256][32], dZ32 [128][32], dZ2 [256][32]
-constexpr int kBwdLdsFloats = (32 + 32 + 2 * kH3 + kHM + kH2) * kE;
+// dX down the online net for 32 rows: LDS holds dQ / dQe [32][32], dZ3 / dZ3e [256][32], dZ32 [128][32], dZ2 [W2][32]
+// (120 KiB at W2 = 256, 152 KiB at 512)
+constexpr int bwd_lds_floats(int w2) { return (32 + 32 + 2 * kH3 + kHM + w2) * kE; }
+template <int W2>
 __global__ __launch_bounds__(kThreads) void k_learner_bwd(const LArgs a) {
+    constexpr int kEpsIn31 = NoiseAt<W2>::kEpsIn31, kEpsOut31 = NoiseAt<W2>::kEpsOut31,
+                  kEpsIn41 = NoiseAt<W2>::kEpsIn41;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* DQ = lds;
     float* DQe = DQ + 32 * kE;
@@ -244,7 +295,7 @@ __global__ __launch_bounds__(kThreads) void k_learner_bwd(const LArgs a) {
     __syncthreads();
 
     // ---- fc31^T and fc32^T meet in h2: dH2 = u_w^T dZ3 + W32_eff^T dZ32 + eps_in o (sigma_w^T dZ3e)
-    for (int t = wave; t < tiles(kH2); t += 4) {
+    for (int t = wave; t < tiles(W2); t += 4) {
         f32x16 acc = {}, accs = {};
         gemm_tile(acc, F + a.fo.t31u + (size_t)t * ksteps(kH3) * 64, D3, ksteps(kH3), lane);
         gemm_tile(acc, F + a.fo.t32 + (size_t)t * ksteps(kHM) * 64, D32, ksteps(kHM), lane);
@@ -260,7 +311,7 @@ __global__ __launch_bounds__(kThreads) void k_learner_bwd(const LArgs a) {
     __syncthreads();
 
     // ---- fc2^T: dH1 = W2_eff^T dZ2; ReLU mask of h1
-    dense4(F + a.fo.t2, nullptr, D2, nullptr, kH1, kH2, lane, wave, [&](int o, float y, float) {
+    dense4(F + a.fo.t2, nullptr, D2, nullptr, kH1, W2, lane, wave, [&](int o, float y, float) {
         a.dZ1[(size_t)o * B + eg] = a.H1[(size_t)o * B + eg] > 0.f ? y : 0.f;
     });
 }
@@ -453,6 +504,8 @@ struct qc_learner {
     std::string err;
     bool loaded = false;
     int in_pad = 0, noise_len = 0, A = 0, L = 0, B = 0;
+    int w2 = kH2;             // fc2's width: the instantiation of k_learner_fwd / k_learner_bwd
+    double b1 = 0, b2 = 0;    // LaProp's betas
     // host-side schedule and LaProp scalars (optimizer.py:69-80)
     int64_t updates = 0, step = 0;
     int backup_counter = 0;
@@ -481,7 +534,7 @@ struct qc_learner {
 namespace {
 CreateError g_learner_err;
 
-constexpr double kBeta1 = 0.9, kBeta2 = 0.9995, kEps = 1e-15;   // RL.py:145
+constexpr double kBeta1 = 0.9, kBeta2 = 0.9995, kEps = 1e-15;   // the defaults: IHO / IQO / QO RL.py:144-145
 constexpr int kCenteredAfter = 10;                               // optimizer.py:9
 
 // tensor indices of layer l (fc1, fc2, fc31, fc41, fc32, fc42): weight, bias, then g | sigma_w, sigma_b
@@ -514,19 +567,19 @@ void free_all(qc_learner* l) {
 // optimizer step + fragment preparation (the tail of an update, and qc_learner_apply)
 void optimizer_and_prep(qc_learner* l, int chain) {
     l->step += 1;
-    l->l1 = l->l1 * kBeta1 + (1 - kBeta1) * l->lr;
-    l->l2 = l->l2 * kBeta2 + (1 - kBeta2);
+    l->l1 = l->l1 * l->b1 + (1 - l->b1) * l->lr;
+    l->l2 = l->l2 * l->b2 + (1 - l->b2);
     OptArgs o{};
     o.P = l->P; o.G = l->G; o.E = l->E; o.V = l->V; o.MU = l->MU;
     o.dot = l->d_dot;
     o.norm = l->d_norm;
     o.chain = chain;
     o.centered = l->step > kCenteredAfter ? 1 : 0;
-    o.beta1 = (float)kBeta1;
-    o.beta2 = (float)kBeta2;
-    o.omb2 = (float)(1 - kBeta2);
+    o.beta1 = (float)l->b1;
+    o.beta2 = (float)l->b2;
+    o.omb2 = (float)(1 - l->b2);
     o.l2 = (float)l->l2;
-    o.elr = (float)((1 - kBeta1) * l->lr);
+    o.elr = (float)((1 - l->b1) * l->lr);
     o.step_size = (float)(l->lr != 0. ? 1. / (l->l1 / l->lr) : 1.);
     o.eps = (float)kEps;
     hipLaunchKernelGGL(k_learner_opt, dim3(64, kNT), dim3(256), 0, l->stream, o, l->tt);
@@ -548,6 +601,12 @@ int qc_learner_create(const qc_learner_params* p, int device, qc_learner** out) 
                     QC_EINVAL);
     if (p->backup_period < 1) return fail("backup_period must be >= 1", QC_EINVAL);
     if (!(p->lr >= 0.)) return fail("lr must be >= 0", QC_EINVAL);
+    const int w2 = fc2_width(p->hidden2);
+    if (!w2) return fail("hidden2 must be 0, 256 or 512 (fc2's width)", QC_EINVAL);
+    if (p->target_mode != QC_TD_ALIVE && p->target_mode != QC_TD_REWARD_FAIL && p->target_mode != QC_TD_REWARD)
+        return fail("target_mode must be QC_TD_ALIVE, QC_TD_REWARD_FAIL or QC_TD_REWARD", QC_EINVAL);
+    if (!(p->beta1 >= 0. && p->beta1 < 1.)) return fail("beta1 must be in [0, 1) (0: 0.9)", QC_EINVAL);
+    if (!(p->beta2 >= 0. && p->beta2 < 1.)) return fail("beta2 must be in [0, 1) (0: 0.9995)", QC_EINVAL);
     if (const int rc = check_device(device, g_learner_err, "the learner")) return rc;
 
     qc_learner* l = new qc_learner();
@@ -556,11 +615,14 @@ int qc_learner_create(const qc_learner_params* p, int device, qc_learner** out) 
     l->lr = p->lr;
     const int L = l->L = p->data_length, A = l->A = p->n_actions, B = l->B = p->batch_size;
     l->in_pad = in_pad(L);
-    l->noise_len = noise_len(A);
+    l->w2 = w2;
+    l->b1 = p->beta1 != 0. ? p->beta1 : kBeta1;
+    l->b2 = p->beta2 != 0. ? p->beta2 : kBeta2;
+    l->noise_len = noise_len(w2, A);
 
     // ---- parameter tensors (offsets in multiples of 4 floats)
-    const int O[6] = {kH1, kH2, kH3, A, kHM, 1};
-    const int K[6] = {L, kH1, kH2, kH3, kH2, kHM};
+    const int O[6] = {kH1, w2, kH3, A, kHM, 1};
+    const int K[6] = {L, kH1, w2, kH3, w2, kHM};
     int off = 0, nwn = 0;
     int wn_of[6] = {-1, -1, -1, -1, -1, -1};
     int wnt[4] = {0, 0, 0, 0};
@@ -589,7 +651,7 @@ int qc_learner_create(const qc_learner_params* p, int device, qc_learner** out) 
     l->wn_tensors = int4{wnt[0], wnt[1], wnt[2], wnt[3]};
 
     // ---- fragment buffer: forward fragments and padded biases, then the transposed fragments
-    const int Kp[6] = {l->in_pad, kH1, kH2, kH3, kH2, kHM};
+    const int Kp[6] = {l->in_pad, kH1, w2, kH3, w2, kHM};
     int fo = frag_layout(6, O, Kp, kNoisy, l->fo.u, l->fo.s, l->fo.ub, l->fo.sb);
     l->nf_fwd = fo;
     auto tfrag = [&](int j, int kpad) {   // fragments of W_j^T: [K_j rows][O_j pad kpad]
@@ -597,7 +659,7 @@ int qc_learner_create(const qc_learner_params* p, int device, qc_learner** out) 
         fo += tiles(K[j]) * ksteps(kpad) * 64;
         return at;
     };
-    l->fo.t2 = tfrag(1, kH2);
+    l->fo.t2 = tfrag(1, w2);
     l->fo.t31u = tfrag(2, kH3);
     l->fo.t31s = tfrag(2, kH3);
     l->fo.t41u = tfrag(3, 32);
@@ -618,7 +680,7 @@ int qc_learner_create(const qc_learner_params* p, int device, qc_learner** out) 
         const Tensor* T = &l->tt.t[kFirst[j]];
         prep.push_back(PrepJob{T[sigma ? 2 : 0].off, kNoisy[j] ? -1 : T[2].off, -1, O[j], K[j], 1, kpad, out_off, -1, -1});
     };
-    tjob(1, 0, kH2, l->fo.t2);
+    tjob(1, 0, w2, l->fo.t2);
     tjob(2, 0, kH3, l->fo.t31u);
     tjob(2, 1, kH3, l->fo.t31s);
     tjob(3, 0, 32, l->fo.t41u);
@@ -636,11 +698,11 @@ int qc_learner_create(const qc_learner_params* p, int device, qc_learner** out) 
         return at;
     };
     const size_t oQ = take((size_t)3 * B * 32), oM = take((size_t)3 * B), oN = take((size_t)l->noise_len * kChunks);
-    const size_t oX0 = take((size_t)x0_rows * B), oH1 = take((size_t)kH1 * B), oH2 = take((size_t)kH2 * B),
-                 oH2e = take((size_t)kH2 * B), oA3 = take((size_t)kH3 * B), oA3e = take((size_t)kH3 * B),
+    const size_t oX0 = take((size_t)x0_rows * B), oH1 = take((size_t)kH1 * B), oH2 = take((size_t)w2 * B),
+                 oH2e = take((size_t)w2 * B), oA3 = take((size_t)kH3 * B), oA3e = take((size_t)kH3 * B),
                  oR32 = take((size_t)kHM * B), odQ = take((size_t)32 * B), odQe = take((size_t)32 * B),
                  odM = take((size_t)32 * B), odZ3 = take((size_t)kH3 * B), odZ3e = take((size_t)kH3 * B),
-                 odZ32 = take((size_t)kHM * B), odZ2 = take((size_t)kH2 * B), odZ1 = take((size_t)kH1 * B);
+                 odZ32 = take((size_t)kHM * B), odZ2 = take((size_t)w2 * B), odZ1 = take((size_t)kH1 * B);
     const size_t oLoss = take(4), oNorm = take(4);
     l->ws_floats = w;
 
@@ -686,10 +748,10 @@ int qc_learner_create(const qc_learner_params* p, int device, qc_learner** out) 
     float* G = l->G;
     auto gt = [&](int ti) { return G + l->tt.t[ti].off; };
     const DwJob jobs[8] = {
-        {k.dZ1, k.X0, gt(0), gt(1), kH1, L},        {k.dZ2, k.H1, gt(3), gt(4), kH2, kH1},
-        {k.dZ3, k.H2, gt(6), gt(7), kH3, kH2},      {k.dZ3e, k.H2e, gt(8), gt(9), kH3, kH2},
+        {k.dZ1, k.X0, gt(0), gt(1), kH1, L},        {k.dZ2, k.H1, gt(3), gt(4), w2, kH1},
+        {k.dZ3, k.H2, gt(6), gt(7), kH3, w2},       {k.dZ3e, k.H2e, gt(8), gt(9), kH3, w2},
         {k.dQ, k.A3, gt(10), gt(11), A, kH3},       {k.dQe, k.A3e, gt(12), gt(13), A, kH3},
-        {k.dZ32, k.H2, gt(14), gt(15), kHM, kH2},   {k.dM, k.R32, gt(17), gt(18), 1, kHM},
+        {k.dZ32, k.H2, gt(14), gt(15), kHM, w2},   {k.dM, k.R32, gt(17), gt(18), 1, kHM},
     };
     std::vector<int4> tl;
     for (int j = 0; j < 8; ++j)
@@ -701,11 +763,11 @@ int qc_learner_create(const qc_learner_params* p, int device, qc_learner** out) 
     if (e == hipSuccess) e = hipMalloc(&l->d_tiles, tl.size() * sizeof(int4));
     if (e == hipSuccess) e = hipMemcpy(l->d_tiles, tl.data(), tl.size() * sizeof(int4), hipMemcpyHostToDevice);
     if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)k_learner_fwd, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kLdsFloats * (int)sizeof(float));
+        e = hipFuncSetAttribute(w2 == kH2Wide ? (const void*)k_learner_fwd<kH2Wide> : (const void*)k_learner_fwd<kH2>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsFloats * (int)sizeof(float));
     if (e == hipSuccess)
-        e = hipFuncSetAttribute((const void*)k_learner_bwd, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kBwdLdsFloats * (int)sizeof(float));
+        e = hipFuncSetAttribute(w2 == kH2Wide ? (const void*)k_learner_bwd<kH2Wide> : (const void*)k_learner_bwd<kH2>,
+                                hipFuncAttributeMaxDynamicSharedMemorySize, bwd_lds_floats(w2) * (int)sizeof(float));
     if (e != hipSuccess) {
         free_all(l);
         delete l;
@@ -818,10 +880,16 @@ int qc_learner_update(qc_learner* l, const float* transitions, const float* is_w
     }
     LArgs k = l->k;
     k.trans = transitions;
-    hipLaunchKernelGGL(k_learner_fwd, dim3(3 * B / kE), dim3(kThreads), kLdsFloats * sizeof(float), l->stream, k);
+    const bool wide = l->w2 == kH2Wide;
+    if (wide)
+        hipLaunchKernelGGL(k_learner_fwd<kH2Wide>, dim3(3 * B / kE), dim3(kThreads), kLdsFloats * sizeof(float), l->stream, k);
+    else
+        hipLaunchKernelGGL(k_learner_fwd<kH2>, dim3(3 * B / kE), dim3(kThreads), kLdsFloats * sizeof(float), l->stream, k);
     LossArgs s{};
     s.Q = k.Q; s.M = k.M; s.trans = transitions; s.w = is_weights; s.noise = l->d_noise;
     s.B = B; s.n_act = l->A; s.in_len = l->L; s.row_len = k.row_len; s.rpc = k.rpc;
+    s.eps_out41 = l->w2 + 2 * kH3;
+    s.omg = (float)(1. - l->p.gamma);
     s.gamma = (float)l->p.gamma;
     s.rew = (float)((1. - l->p.gamma) * l->p.alive_reward);
     s.failing = (float)l->p.failing_reward;
@@ -829,8 +897,17 @@ int qc_learner_update(qc_learner* l, const float* transitions, const float* is_w
     s.inv_A = (float)(1. / l->A);
     s.dQ = k.dQ; s.dQe = k.dQe; s.dM = k.dM; s.ul = unweighted_loss; s.loss = l->d_loss; s.loss_user = loss;
     s.cnt = l->d_cnt;
-    hipLaunchKernelGGL(k_learner_loss, dim3(1), dim3(1024), 0, l->stream, s);
-    hipLaunchKernelGGL(k_learner_bwd, dim3(B / kE), dim3(kThreads), kBwdLdsFloats * sizeof(float), l->stream, k);
+    if (l->p.target_mode == QC_TD_REWARD_FAIL)
+        hipLaunchKernelGGL(k_learner_loss<QC_TD_REWARD_FAIL>, dim3(1), dim3(1024), 0, l->stream, s);
+    else if (l->p.target_mode == QC_TD_REWARD)
+        hipLaunchKernelGGL(k_learner_loss<QC_TD_REWARD>, dim3(1), dim3(1024), 0, l->stream, s);
+    else
+        hipLaunchKernelGGL(k_learner_loss<QC_TD_ALIVE>, dim3(1), dim3(1024), 0, l->stream, s);
+    if (wide)
+        hipLaunchKernelGGL(k_learner_bwd<kH2Wide>, dim3(B / kE), dim3(kThreads), bwd_lds_floats(kH2Wide) * sizeof(float),
+                           l->stream, k);
+    else
+        hipLaunchKernelGGL(k_learner_bwd<kH2>, dim3(B / kE), dim3(kThreads), bwd_lds_floats(kH2) * sizeof(float), l->stream, k);
     hipLaunchKernelGGL(k_learner_dw, dim3((l->ntiles + 3) / 4), dim3(kThreads), 0, l->stream, l->d_dwjobs, l->d_tiles,
                        l->ntiles, B);
     hipLaunchKernelGGL(k_learner_wndot, dim3(4), dim3(1024), 0, l->stream, l->P, l->G, l->wn_tensors, l->tt, l->d_dot);

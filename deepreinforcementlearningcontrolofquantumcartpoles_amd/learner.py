@@ -16,6 +16,19 @@ oscillator/RL.py:159-232, optimizer.py). `DQNLearner` does one such update in ei
 `batch_size` must be a multiple of 128 (at most 4096): the learner implements FactorizedNoisy's batched
 branch, 32 noise samples per batch, one per chunk of batch_size / 32 rows (layers.py:57-74); other batch sizes
 take the reference's per-row branch, which is refused (ValueError). Only direct_DQN(noisy_layers=2) is covered.
+
+The reference's four drivers differ in fc2's width, the TD target and LaProp's betas; the constructor takes all
+three (defaults: the inverted harmonic driver's):
+
+    driver               hidden2   target          betas
+    inverted harmonic    256       "alive"         (0.9, 0.9995)
+    inverted quartic     512       "alive"         (0.9, 0.9995)
+    quartic              512       "reward_fail"   (0.9, 0.9995)
+    harmonic             256       "reward"        (0.9, 0.999)
+
+"alive": y = gamma nsv + (1 - gamma) alive_reward, 0 where the row's reward == failing_reward; "reward_fail":
+y = gamma nsv + (1 - gamma) reward, the reward itself where it is <= failing_reward; "reward": the same with no
+fail rule.
 """
 from __future__ import annotations
 
@@ -25,26 +38,28 @@ from typing import Mapping, Optional
 import torch
 
 from . import _lib as L
-from .actor import _layer_tensors
+from .actor import _layer_tensors, fc2_width
 from .replay import _view
 
 LAYERS = ("fc1", "fc2", "fc31", "fc41", "fc32", "fc42")
 NOISY = (False, False, True, True, False, False)
 
 
-def _shapes(data_length: int, n_actions: int):
-    return ((512, data_length), (256, 512), (256, 256), (n_actions, 256), (128, 256), (1, 128))
+def _shapes(data_length: int, n_actions: int, hidden2: int = 256):
+    return ((512, data_length), (hidden2, 512), (256, hidden2), (n_actions, 256), (128, hidden2), (1, 128))
 
 
 class DQNLearner(L.DeviceHandle):
-    """TrainDQN for direct_DQN(data_length, noisy_layers=2) with LaProp(centered, betas (0.9, 0.9995))."""
+    """TrainDQN for direct_DQN(data_length, noisy_layers=2) with LaProp(centered, betas); hidden2 (None: from
+    `fc2.weight`), target and betas select the driver (module docstring)."""
 
     _prefix = "qc_learner"
 
     def __init__(self, params: Mapping[str, torch.Tensor], batch_size: int = 512, gamma: float = 0.998,
                  lr: float = 4e-4, alive_reward: float = 10., failing_reward: float = -1., backup_period: int = 300,
                  device: int | str | torch.device = 0, seed: int = 0, data_length: Optional[int] = None,
-                 n_actions: Optional[int] = None):
+                 n_actions: Optional[int] = None, hidden2: Optional[int] = None, target: str = "alive",
+                 betas=(0.9, 0.9995)):
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("DQNLearner runs on a HIP device only (no CPU fallback)")
@@ -55,6 +70,16 @@ class DQNLearner(L.DeviceHandle):
                              "noise branch; the per-row branch of other sizes is not implemented)")
         if "fc1.weight" not in params or "fc41.u_w" not in params:
             raise ValueError("params must be a direct_DQN(noisy_layers=2) state_dict (fc1.weight, ..., fc41.u_w)")
+        if "fc2.weight" not in params:
+            raise ValueError("params must be a direct_DQN(noisy_layers=2) state_dict (fc2.weight is missing)")
+        self.hidden2 = fc2_width(params, hidden2)
+        if target not in L.TD_TARGETS:
+            raise ValueError(f"target must be one of {sorted(L.TD_TARGETS)}, not {target!r}")
+        self.target = target
+        self.betas = (float(betas[0]), float(betas[1]))
+        for name, b in zip(("beta1", "beta2"), self.betas):
+            if not 0. < b < 1.:
+                raise ValueError(f"{name} (betas) must be in (0, 1), not {b}")
         self.data_length = int(data_length if data_length is not None else params["fc1.weight"].shape[1])
         self.n_actions = int(n_actions if n_actions is not None else params["fc41.u_w"].shape[0])
         self.batch_size = int(batch_size)
@@ -63,6 +88,8 @@ class DQNLearner(L.DeviceHandle):
         p.data_length, p.n_actions, p.batch_size = self.data_length, self.n_actions, self.batch_size
         p.backup_period, p.gamma, p.lr = int(backup_period), float(gamma), float(lr)
         p.alive_reward, p.failing_reward, p.seed = float(alive_reward), float(failing_reward), int(seed)
+        p.hidden2, p.target_mode = self.hidden2, L.TD_TARGETS[target]
+        p.beta1, p.beta2 = self.betas
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             torch.cuda.init()
@@ -77,7 +104,7 @@ class DQNLearner(L.DeviceHandle):
     def _layer_array(self, params: Mapping[str, torch.Tensor]):
         layers = (L.QcDqnLayer * 6)()
         keep = []
-        for i, (name, shape) in enumerate(zip(LAYERS, _shapes(self.data_length, self.n_actions))):
+        for i, (name, shape) in enumerate(zip(LAYERS, _shapes(self.data_length, self.n_actions, self.hidden2))):
             if NOISY[i] != (f"{name}.u_w" in params):
                 raise ValueError(f"{name}: the learner covers direct_DQN(noisy_layers=2) only")
             t = _layer_tensors(params, name, self.device)
@@ -98,7 +125,7 @@ class DQNLearner(L.DeviceHandle):
 
     def _tensors(self, layers) -> dict:
         out = {}
-        for i, (name, (o, k)) in enumerate(zip(LAYERS, _shapes(self.data_length, self.n_actions))):
+        for i, (name, (o, k)) in enumerate(zip(LAYERS, _shapes(self.data_length, self.n_actions, self.hidden2))):
             ly = layers[i]
             if NOISY[i]:
                 out[f"{name}.u_w"] = _view(ly.weight, o * k, torch.float32, self.device).view(o, k)
@@ -177,7 +204,12 @@ class DQNLearner(L.DeviceHandle):
         return ul
 
     def push(self, actor):
-        """Load the online fc1, fc2, fc31, fc41 into a DQNActor, device to device (no host copy)."""
+        """Load the online fc1, fc2, fc31, fc41 into a DQNActor, device to device (no host copy). The actor's
+        net must be the learner's: the load reads the tensors at the actor's own sizes."""
+        if (actor.hidden2, actor.data_length, actor.n_actions) != (self.hidden2, self.data_length, self.n_actions):
+            raise ValueError(f"push: the actor's net (hidden2 {actor.hidden2}, data_length {actor.data_length}, "
+                             f"n_actions {actor.n_actions}) is not the learner's (hidden2 {self.hidden2}, "
+                             f"data_length {self.data_length}, n_actions {self.n_actions})")
         layers = (L.QcDqnLayer * 6)()
         self._check(L.lib().qc_learner_layers(self._h, 0, layers))
         with torch.cuda.device(self.device):

@@ -293,9 +293,11 @@ int qc_group_layout(qc_handle* h, int32_t* order, int64_t order_len, int32_t* mi
  * (inverted harmonic oscillator/RL.py:80-111 + layers.py FactorizedNoisy / Linear_weight_normalize),
  * evaluated for B envs at once on the device, with the actor's epsilon-greedy choice
  * (IHO/main_parallel.py:208-219), replacing the per-actor pipe to the inference process
- * (IHO/main_parallel.py:414-440). Layers: fc1 (in -> 512), fc2 (512 -> 256), fc31 (256 -> 256),
+ * (IHO/main_parallel.py:414-440). Layers: fc1 (in -> 512), fc2 (512 -> H2), fc31 (H2 -> 256),
  * fc41 (256 -> n_actions), ReLU between; actions = argmax of fc41 (the mean branch fc32/fc42 does not
- * enter the action). fp32 throughout (the reference net's dtype), f32-input MFMA. */
+ * enter the action). H2 = 256 is the harmonic and inverted harmonic drivers' net, H2 = 512 the quartic and
+ * inverted quartic drivers' (their RL.py:87-93); it is fixed at create. fp32 throughout (the reference
+ * net's dtype), f32-input MFMA. */
 typedef struct qc_actor qc_actor;
 
 typedef struct qc_dqn_params {
@@ -303,6 +305,7 @@ typedef struct qc_dqn_params {
     int32_t n_actions;     /* 21 */
     int64_t max_batch;     /* largest B passed to qc_actor_act */
     uint64_t seed;         /* Philox key of the NoisyNet noise and the epsilon-greedy draws */
+    int32_t hidden2;       /* H2, fc2's width: 0 or 256, or 512; anything else is QC_EINVAL */
 } qc_dqn_params;
 
 /* One layer's parameters (device fp32 pointers, the reference state_dict tensors):
@@ -326,9 +329,9 @@ int qc_actor_set_stream(qc_actor* a, void* stream);
  * computes the effective weights and stores them in the kernels' fragment order on the device */
 int qc_actor_load(qc_actor* a, const qc_dqn_layer layers[4]);
 
-/* Noise of the factorised noisy layers per env: eps_in(fc31)[256], eps_out(fc31)[256],
+/* Noise of the factorised noisy layers per env: eps_in(fc31)[H2], eps_out(fc31)[256],
  * eps_in(fc41)[256], eps_out(fc41)[n_actions], each f(z) = sign(z) sqrt|z| of a standard normal z
- * (layers.py:77-79): qc_actor_noise_len() floats per env. */
+ * (layers.py:77-79): qc_actor_noise_len() = H2 + 512 + n_actions floats per env (789 / 1045 at 21 actions). */
 int qc_actor_noise_len(const qc_actor* a);
 
 /* One action per env: obs [B][data_length] fp32 (device): the network input exactly as the actor hands it
@@ -434,10 +437,12 @@ int qc_replay_buffers(const qc_replay* r, const double** tree, const float** dat
  * Device DQN learner: the reference's TrainDQN.__call__ (inverted harmonic oscillator/RL.py:159-232)
  * with its LaProp optimizer (optimizer.py; centered, betas (0.9, 0.9995), eps 1e-15, RL.py:145) for the
  * 'xp' network direct_DQN(data_length, noisy_layers = 2): fc1, fc2, fc31 (noisy), fc41 (noisy) and the mean
- * head fc32, fc42, fp32 throughout on f32-input MFMA. One update: the target network follows the online
+ * head fc32, fc42, fp32 throughout on f32-input MFMA. fc2's width H2 (hidden2), the TD target (target_mode)
+ * and LaProp's betas are what the reference's four drivers differ in; the zero defaults are the inverted
+ * harmonic driver's (H2 = 256, QC_TD_ALIVE, betas (0.9, 0.9995)). One update: the target network follows the online
  * one when backup_counter == 0, then backup_counter = (backup_counter + 1) % backup_period; double-DQN
  * target a* = argmax Q_online(next), sav = Q(prev)[a] + m(prev) - mean Q(prev), nsv the same of the target
- * net at a*, y = gamma nsv + (1 - gamma) alive_reward (0 where reward == failing_reward), ul = (sav - y)^2,
+ * net at a*, the target y by target_mode (below), ul = (sav - y)^2,
  * loss = mean(ul w); backward through the online pass on prev; one LaProp step. The NoisyNet noise is
  * FactorizedNoisy's batched branch (layers.py:57-74): the batch is 32 contiguous chunks of B / 32 rows,
  * one (eps_in, eps_out) pair per chunk and noisy layer, shared by the three forward passes. That branch
@@ -445,12 +450,20 @@ int qc_replay_buffers(const qc_replay* r, const double** tree, const float** dat
  * Gradients use no atomics: the same inputs give bit-identical parameters. All pointers are device
  * pointers; every call is asynchronous on the learner's stream except qc_learner_stats. */
 typedef struct qc_learner qc_learner;
+/* The TD target y of a row with reward r (the last column of a transition):
+ *   QC_TD_ALIVE        y = gamma nsv + (1 - gamma) alive_reward; y = 0 where r == failing_reward (IHO, IQO)
+ *   QC_TD_REWARD_FAIL  y = gamma nsv + (1 - gamma) r;            y = r where r <= failing_reward (QO)
+ *   QC_TD_REWARD       y = gamma nsv + (1 - gamma) r             (HO; alive_reward / failing_reward unused) */
+enum { QC_TD_ALIVE = 0, QC_TD_REWARD_FAIL = 1, QC_TD_REWARD = 2 };
 typedef struct qc_learner_params {
     int32_t data_length, n_actions;
     int32_t batch_size;            /* multiple of 128, <= 4096 */
     int32_t backup_period;
     double gamma, lr, alive_reward, failing_reward;
     uint64_t seed;                 /* Philox key of the in-kernel noise */
+    int32_t hidden2;               /* H2, fc2's width: 0 or 256, or 512 (as qc_dqn_params) */
+    int32_t target_mode;           /* QC_TD_*; others are QC_EINVAL */
+    double beta1, beta2;           /* LaProp's betas in [0, 1); 0: 0.9 and 0.9995 */
 } qc_learner_params;
 
 typedef struct qc_learner_stats_t {
