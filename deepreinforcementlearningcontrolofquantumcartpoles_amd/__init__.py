@@ -7,7 +7,16 @@ Modules:
   simulation  drop-in surface of the reference `simulation` extension (B = 1)
   env         BatchedEnv: reset/step/observation semantics of the reference drivers, batched
   distributed env sharding over ranks + RCCL gather of episode returns
+  learner     DQNLearner / MeasurementLearner: the reference's TrainDQN update on the device
 """
 from .config import DEFAULTS, HO, IHO, IQO, QO, Physics  # noqa: F401
 
-__all__ = ["DEFAULTS", "HO", "IHO", "QO", "IQO", "Physics"]
+__all__ = ["DEFAULTS", "HO", "IHO", "QO", "IQO", "Physics", "DQNLearner", "MeasurementLearner"]
+
+
+def __getattr__(name):
+    # the learners need torch: imported on first use, so `import <package>` stays light
+    if name in ("DQNLearner", "MeasurementLearner"):
+        from . import learner
+        return getattr(learner, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

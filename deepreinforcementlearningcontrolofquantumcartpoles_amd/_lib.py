@@ -45,6 +45,9 @@ EXPORTS = (
     "qc_learner_create", "qc_learner_destroy", "qc_learner_last_error", "qc_learner_set_stream",
     "qc_learner_noise_len", "qc_learner_load", "qc_learner_layers", "qc_learner_update", "qc_learner_set_lr",
     "qc_learner_stats", "qc_learner_grads", "qc_learner_apply",
+    "qc_mlearner_create", "qc_mlearner_destroy", "qc_mlearner_last_error", "qc_mlearner_set_stream",
+    "qc_mlearner_noise_len", "qc_mlearner_load", "qc_mlearner_layers", "qc_mlearner_update", "qc_mlearner_set_lr",
+    "qc_mlearner_stats", "qc_mlearner_grads", "qc_mlearner_apply", "qc_mlearner_states",
 )
 
 
@@ -144,6 +147,24 @@ class QcLearnerParams(ctypes.Structure):
         ("target_mode", ctypes.c_int32),
         ("beta1", ctypes.c_double),
         ("beta2", ctypes.c_double),
+    ]
+
+
+class QcMlearnerParams(ctypes.Structure):
+    _fields_ = [
+        ("read_length", ctypes.c_int32),
+        ("read_step_length", ctypes.c_int32),
+        ("n_actions", ctypes.c_int32),
+        ("batch_size", ctypes.c_int32),
+        ("backup_period", ctypes.c_int32),
+        ("target_mode", ctypes.c_int32),
+        ("gamma", ctypes.c_double),
+        ("lr", ctypes.c_double),
+        ("alive_reward", ctypes.c_double),
+        ("failing_reward", ctypes.c_double),
+        ("beta1", ctypes.c_double),
+        ("beta2", ctypes.c_double),
+        ("seed", ctypes.c_uint64),
     ]
 
 
@@ -324,6 +345,21 @@ def lib() -> ctypes.CDLL:
     L.qc_learner_stats.argtypes = [vp, P(QcLearnerStats)]
     L.qc_learner_grads.argtypes = [vp, P(QcDqnLayer)]
     L.qc_learner_apply.argtypes = [vp, P(QcDqnLayer)]
+    L.qc_mlearner_create.argtypes = [P(QcMlearnerParams), ctypes.c_int, P(vp)]
+    L.qc_mlearner_destroy.argtypes = [vp]
+    L.qc_mlearner_destroy.restype = None
+    L.qc_mlearner_last_error.argtypes = [vp]
+    L.qc_mlearner_last_error.restype = ctypes.c_char_p
+    L.qc_mlearner_set_stream.argtypes = [vp, vp]
+    L.qc_mlearner_noise_len.argtypes = [vp]
+    L.qc_mlearner_load.argtypes = [vp, P(QcDqnLayer)]
+    L.qc_mlearner_layers.argtypes = [vp, ctypes.c_int, P(QcDqnLayer)]
+    L.qc_mlearner_update.argtypes = [vp, vp, vp, vp, u64, vp, vp]
+    L.qc_mlearner_set_lr.argtypes = [vp, d]
+    L.qc_mlearner_stats.argtypes = [vp, P(QcLearnerStats)]
+    L.qc_mlearner_grads.argtypes = [vp, P(QcDqnLayer)]
+    L.qc_mlearner_apply.argtypes = [vp, P(QcDqnLayer)]
+    L.qc_mlearner_states.argtypes = [vp, vp, vp, vp]
     if isinstance(L, _Tolerant):
         L = L.lib
     for name in EXPORTS:
@@ -366,6 +402,7 @@ check = _checker("qc")
 check_actor = _checker("qc_actor")
 check_mactor = _checker("qc_mactor")
 check_learner = _checker("qc_learner")
+check_mlearner = _checker("qc_mlearner")
 check_replay = _checker("qc_replay")
 
 

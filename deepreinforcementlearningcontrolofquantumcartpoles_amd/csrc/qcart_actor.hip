@@ -15,6 +15,7 @@
 #include "../../include/qcart.h"
 #include "qcart_dqn.hpp"
 #include "qcart_host.hpp"
+#include "qcart_learner.hpp"
 
 namespace qcart {
 namespace actor {
@@ -815,3 +816,27 @@ int qc_mactor_act(qc_mactor* a, int64_t B, int64_t env_offset, const float* obs,
 }
 
 }  // extern "C"
+
+// ---- the measurement network's forward stack for the measurement learner (qcart_learner.hpp) ----
+namespace qcart {
+namespace actor {
+void launch_mtr(hipStream_t s, const float* in, float* out, int F, int64_t nb, int64_t ld, int64_t c0) {
+    hipLaunchKernelGGL(k_mtr, dim3((unsigned)((F + 63) / 64), (unsigned)((nb + 63) / 64)), dim3(256), 0, s, in, out, F, nb,
+                       ld, c0);
+}
+void launch_mnet_fwd(hipStream_t s, const MnetFwd& a) {
+    const int64_t n1 = a.nb * a.T1, n2 = a.nb * a.T2, n3 = a.nb * a.T3;
+    const int flat = 64 * a.T3;
+    hipLaunchKernelGGL((k_mconv<2, 13, 5, 1, kNT1, kNA1, kQ1>), dim3((unsigned)((n1 + 128 * kNT1 - 1) / (128 * kNT1))),
+                       dim3(256), 0, s, a.x, a.L, a.wf[0], a.bias[0], a.y1, a.T1, n1);
+    hipLaunchKernelGGL((k_mconv<32, 11, 4, 2, kNT2, kNA2, kQ2>), dim3((unsigned)((n2 + 128 * kNT2 - 1) / (128 * kNT2))),
+                       dim3(256), 0, s, a.y1, a.T1, a.wf[1], a.bias[1], a.y2, a.T2, n2);
+    hipLaunchKernelGGL((k_mconv<64, 9, 4, 2, kNT3, kNA3, kQ3>), dim3((unsigned)((n3 + 128 * kNT3 - 1) / (128 * kNT3))),
+                       dim3(256), 0, s, a.y2, a.T2, a.wf[2], a.bias[2], a.y3e, a.T3, n3);
+    launch_mtr(s, a.y3e, a.y3f, flat, a.nb, a.ld, a.c0);
+    constexpr int envs_per_wg = (4 / (8 / kMfcMT)) * kMfcNT * 32;
+    hipLaunchKernelGGL((k_mfc<kMfcMT, kMfcNT>), dim3((unsigned)((a.nb + envs_per_wg - 1) / envs_per_wg)), dim3(256), 0, s,
+                       a.y3f + a.c0, a.ld, flat, a.wf[3], a.bias[3], a.h + a.c0, a.nb);
+}
+}  // namespace actor
+}  // namespace qcart

@@ -20,6 +20,9 @@
 //   8 k_learner_prep   ||W||_F, effective weights -> forward and transposed fragments
 // The target network is a copy of the parameters and of the forward fragments (two device-to-device
 // copies every backup_period updates).
+// The table-driven kernels (noise, loss, dw, wndot, opt, prep) and the <256, true> instantiations of k_learner_fwd /
+// k_learner_bwd (the measurement network's tail) also serve the measurement learner (qcart_mlearner.hip) through the
+// launchers at the end of the namespace (qcart_learner.hpp).
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -29,41 +32,24 @@
 #include "../../include/qcart.h"
 #include "qcart_dqn.hpp"
 #include "qcart_host.hpp"
+#include "qcart_learner.hpp"
 
 namespace qcart {
 namespace learner {
 
 using namespace qcart::dqn;
-constexpr int kChunks = 32;        // FactorizedNoisy.forward: n = 32 noise samples per batch (layers.py:58)
-constexpr int kNT = 20;            // parameter tensors
-constexpr int kLdsFloats = kActLdsFloats + kHM * kE;   // the actor's plan, then R32 [128][32]
-
-// offsets into the fragment buffer (floats): forward part first (copied to the target), then transposed
-struct FragOff {
-    int u[6], s[6], ub[6], sb[6];   // fc1, fc2, fc31, fc41, fc32, fc42
-    int t2, t31u, t31s, t41u, t41s, t32, w42;
-};
-
-struct LArgs {
-    const float* F;      // online fragments
-    const float* FT;     // target fragments (forward part)
-    FragOff fo;
-    int in_len, in_pad, n_act, B, row_len, rpc;   // rpc: rows per noise chunk = B / 32
-    const float* trans;
-    const float* noise;  // [noise_len][32]
-    float* Q;            // [3][B][32]
-    float* M;            // [3][B]
-    // feature-major [rows][B] workspace of the online/prev pass and of the backward
-    float *X0, *H1, *H2, *H2e, *A3, *A3e, *R32;
-    float *dQ, *dQe, *dM, *dZ3, *dZ3e, *dZ32, *dZ2, *dZ1;
-};
+constexpr int kNT = 20;            // direct_DQN's parameter tensors
 
 __device__ __forceinline__ float nz(const LArgs& a, int f, int row) { return a.noise[f * kChunks + row / a.rpc]; }
 
 // W2: fc2's width. At W2 = 512 the LDS plan is the wide actor's (qcart_dqn.hpp): eps_in o H2 over the dead H1,
 // fc31's output held in registers across one barrier; fc32 reads H2 before that barrier
-template <int W2>
+// HIN: the measurement network's tail (DQN_measurement, RL.py:68-74): fc1 / fc2 are skipped, relu(fc1) of
+// the convolutional stack (a.h_in, feature-major) enters as H2 at W2 = 256, and fo's fc31 / fc41 / fc32 / fc42
+// slots hold fc21 / fc31 / fc22 / fc32
+template <int W2, bool HIN = false>
 __global__ __launch_bounds__(kThreads) void k_learner_fwd(const LArgs a) {
+    static_assert(!HIN || W2 == kH2, "the measurement network's tail exists at H2 = 256 only");
     constexpr int kEpsIn31 = NoiseAt<W2>::kEpsIn31, kEpsOut31 = NoiseAt<W2>::kEpsOut31,
                   kEpsIn41 = NoiseAt<W2>::kEpsIn41, kEpsOut41 = NoiseAt<W2>::kEpsOut41;
     constexpr bool kWide = W2 != kH2;
@@ -81,6 +67,23 @@ __global__ __launch_bounds__(kThreads) void k_learner_fwd(const LArgs a) {
     const bool ws = pass == 1;
     const int B = a.B;
 
+    float* H2 = RB;
+    float* H2e = kWide ? RA : RB + kH2 * kE;   // wide: over H1, once fc2 is complete
+    if constexpr (HIN) {
+        // ---- relu(fc1) from HBM (coalesced 32-column rows) -> H2, eps_in(fc21) o H2
+        for (int i = tid; i < kH2 * kE; i += kThreads) {
+            const int k = i / kE, e = i % kE;
+            const float h = a.h_in[(size_t)k * a.h_ld + (size_t)pass * B + e0 + e];
+            const float he = h * nz(a, kEpsIn31 + k, e0 + e);
+            H2[i] = h;
+            H2e[i] = he;
+            if (ws) {
+                a.H2[(size_t)k * B + e0 + e] = h;
+                a.H2e[(size_t)k * B + e0 + e] = he;
+            }
+        }
+        __syncthreads();
+    } else {
     for (int i = tid; i < a.in_pad * kE; i += kThreads) {
         const int k = i / kE, e = i % kE;
         const float x = k < a.in_len ? a.trans[(size_t)(e0 + e) * a.row_len + (pass == 1 ? 0 : a.in_len) + k] : 0.f;
@@ -98,8 +101,6 @@ __global__ __launch_bounds__(kThreads) void k_learner_fwd(const LArgs a) {
     __syncthreads();
 
     // ---- fc2: ReLU; eps_in(fc31) o H2
-    float* H2 = RB;
-    float* H2e = kWide ? RA : RB + kH2 * kE;   // wide: over H1, once fc2 is complete
     dense4(F + a.fo.u[1], nullptr, RA, nullptr, W2, kH1, lane, wave, [&](int o, float y, float) {
         const float h = fmaxf(y + F[a.fo.ub[1] + o], 0.f);
         if constexpr (kWide) {
@@ -125,6 +126,7 @@ __global__ __launch_bounds__(kThreads) void k_learner_fwd(const LArgs a) {
         }
         __syncthreads();
     }
+    }   // !HIN
 
     // ---- fc31 (noisy): ReLU; eps_in(fc41) o H3
     float* H3 = RA;
@@ -177,19 +179,6 @@ __global__ __launch_bounds__(kThreads) void k_learner_fwd(const LArgs a) {
              if (lane < 32) a.M[(size_t)pass * B + eg] = m[0] + F[a.fo.ub[5]];
          });
 }
-
-struct LossArgs {
-    const float* Q;
-    const float* M;
-    const float* trans;
-    const float* w;
-    const float* noise;
-    int B, n_act, in_len, row_len, rpc;
-    int eps_out41;   // NoiseAt<W2>::kEpsOut41 of the handle's net
-    float gamma, rew /* (1 - gamma) alive_reward */, omg /* 1 - gamma */, failing, inv_B, inv_A;
-    float *dQ, *dQe, *dM, *ul, *loss, *loss_user;
-    int32_t* cnt;   // [0] non-finite losses, [1] rows with an action outside [0, n_act)
-};
 
 // argmax of Q_online(next) (first index among equal maxima), the two gathers, the TD target, ul, the loss
 // mean and the head gradients dQ [32][B] (rows >= n_act exact zeros), eps_out(fc41) o dQ, dm [B]. MODE: the TD
@@ -254,7 +243,8 @@ __global__ __launch_bounds__(1024) void k_learner_loss(const LossArgs a) {
 // dX down the online net for 32 rows: LDS holds dQ / dQe [32][32], dZ3 / dZ3e [256][32], dZ32 [128][32], dZ2 [W2][32]
 // (120 KiB at W2 = 256, 152 KiB at 512)
 constexpr int bwd_lds_floats(int w2) { return (32 + 32 + 2 * kH3 + kHM + w2) * kE; }
-template <int W2>
+// HIN (the measurement network's tail): stops at dZ2, the gradient at fc1's pre-activation
+template <int W2, bool HIN = false>
 __global__ __launch_bounds__(kThreads) void k_learner_bwd(const LArgs a) {
     constexpr int kEpsIn31 = NoiseAt<W2>::kEpsIn31, kEpsOut31 = NoiseAt<W2>::kEpsOut31,
                   kEpsIn41 = NoiseAt<W2>::kEpsIn41;
@@ -308,6 +298,7 @@ __global__ __launch_bounds__(kThreads) void k_learner_bwd(const LArgs a) {
             a.dZ2[(size_t)o * B + eg] = g;
         }
     }
+    if constexpr (HIN) return;
     __syncthreads();
 
     // ---- fc2^T: dH1 = W2_eff^T dZ2; ReLU mask of h1
@@ -315,15 +306,6 @@ __global__ __launch_bounds__(kThreads) void k_learner_bwd(const LArgs a) {
         a.dZ1[(size_t)o * B + eg] = a.H1[(size_t)o * B + eg] > 0.f ? y : 0.f;
     });
 }
-
-// dW = dY X^T: A = dY [O pad 32][B], X [K pad 32][B] (feature-major, pad rows zero), out [O][K] natural layout
-struct DwJob {
-    const float* A;
-    const float* X;
-    float* out;
-    float* bias;   // row sums of A (the bias gradient), written by the k-tile-0 waves; may be null
-    int O, K;
-};
 
 // one wave per 32x32 output tile; the contraction runs over the whole batch in one fixed order: k-step
 // (j, i) pairs rows b = 8j + i (lanes 0-31) and 8j + 4 + i (lanes 32-63), i = 0..3, from one 16-B load per lane
@@ -363,17 +345,6 @@ __global__ __launch_bounds__(kThreads) void k_learner_dw(const DwJob* __restrict
     }
 }
 
-// parameter tensor table
-struct Tensor {
-    int off, n;
-    int kind;   // 0 plain, 1 weight of a weight-normalised layer, 2 its weight_norm g
-    int wn;     // weight-normalised layer index (kind 1 / 2) or -1
-    int w_off;  // kind 2: offset of the layer's weight
-};
-struct TensorTable {
-    Tensor t[kNT];
-};
-
 // <G, W> over a weight-normalised layer's weight (G = the gradient of the effective weight): fp64, fixed
 // order; tensor ti + 2 is the layer's weight_norm g
 __global__ __launch_bounds__(1024) void k_learner_wndot(const float* __restrict__ P, const float* __restrict__ G,
@@ -390,15 +361,6 @@ __global__ __launch_bounds__(1024) void k_learner_wndot(const float* __restrict_
         dot[4 + T.wn] = (double)P[tt.t[ti + 2].off];   // g before the step: the optimizer updates it in the same launch as W
     }
 }
-
-struct OptArgs {
-    float *P, *G, *E, *V, *MU;
-    const double* dot;    // [4] <G, W>, then [4] the layers' g (k_learner_wndot)
-    const float* norm;    // [4] ||W||_F of the parameters the gradients were taken at
-    int chain;            // 1: G holds effective-weight gradients: apply the weight-norm chain rule first
-    int centered;         // step > 10
-    float beta1, beta2, omb2, l2, elr /* (1 - beta1) lr */, step_size /* 1 / (l1 / lr), or 1 */, eps;
-};
 
 // LaProp (optimizer.py:62-100, centered, no amsgrad, no weight decay) over every tensor; blockIdx.y = tensor
 __global__ __launch_bounds__(256) void k_learner_opt(const OptArgs a, const TensorTable tt) {
@@ -436,14 +398,6 @@ __global__ __launch_bounds__(256) void k_learner_opt(const OptArgs a, const Tens
 }
 
 // effective weight (W g / ||W||_F, or W) -> fragments / a plain vector; bias padded to tiles * 32
-struct PrepJob {
-    int w_off, g_off /* -1: none */, wn /* -1 */, O, K;
-    int mode;        // 0 forward fragments of W [O][K pad], 1 fragments of W^T [K][O pad], 2 plain scaled copy
-    int Kpad;        // padded contraction length of the fragment matrix
-    int out_off;
-    int bias_off /* -1: none */, bias_pad_off;
-};
-constexpr int kPrepParts = 8;
 __global__ __launch_bounds__(1024) void k_learner_prep(const float* __restrict__ P, float* __restrict__ F,
                                                        const PrepJob* __restrict__ jobs, float* __restrict__ norm) {
     __shared__ double part[1024];
@@ -491,6 +445,45 @@ __global__ __launch_bounds__(256) void k_learner_noise(const float* __restrict__
     if (2 * p + 1 < noise_len) out[(2 * p + 1) * kChunks + c] = f.y;
 }
 
+// ---- the launchers of qcart_learner.hpp (the measurement learner drives the same kernels) ----
+void launch_noise(hipStream_t s, const float* in, float* out, int noise_len, uint64_t seed, uint64_t counter) {
+    const int n = in ? kChunks * noise_len : kChunks * ((noise_len + 1) / 2);
+    hipLaunchKernelGGL(k_learner_noise, dim3((n + 255) / 256), dim3(256), 0, s, in, out, noise_len, seed, counter);
+}
+void launch_loss(hipStream_t s, int target_mode, const LossArgs& a) {
+    if (target_mode == QC_TD_REWARD_FAIL)
+        hipLaunchKernelGGL(k_learner_loss<QC_TD_REWARD_FAIL>, dim3(1), dim3(1024), 0, s, a);
+    else if (target_mode == QC_TD_REWARD)
+        hipLaunchKernelGGL(k_learner_loss<QC_TD_REWARD>, dim3(1), dim3(1024), 0, s, a);
+    else
+        hipLaunchKernelGGL(k_learner_loss<QC_TD_ALIVE>, dim3(1), dim3(1024), 0, s, a);
+}
+void launch_dw(hipStream_t s, const DwJob* jobs, const int4* tl, int ntiles, int B) {
+    hipLaunchKernelGGL(k_learner_dw, dim3((ntiles + 3) / 4), dim3(kThreads), 0, s, jobs, tl, ntiles, B);
+}
+void launch_wndot(hipStream_t s, int n_layers, const float* P, const float* G, int4 wn_tensors, const TensorTable& tt,
+                  double* dot) {
+    hipLaunchKernelGGL(k_learner_wndot, dim3(n_layers), dim3(1024), 0, s, P, G, wn_tensors, tt, dot);
+}
+void launch_opt(hipStream_t s, const OptArgs& o, const TensorTable& tt, int nt) {
+    hipLaunchKernelGGL(k_learner_opt, dim3(64, nt), dim3(256), 0, s, o, tt);
+}
+void launch_prep(hipStream_t s, const float* P, float* F, const PrepJob* jobs, int njobs, float* norm) {
+    hipLaunchKernelGGL(k_learner_prep, dim3(njobs, kPrepParts), dim3(1024), 0, s, P, F, jobs, norm);
+}
+bool enable_mtail_lds() {
+    return hipFuncSetAttribute((const void*)k_learner_fwd<kH2, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               kLdsFloats * (int)sizeof(float)) == hipSuccess &&
+           hipFuncSetAttribute((const void*)k_learner_bwd<kH2, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                               bwd_lds_floats(kH2) * (int)sizeof(float)) == hipSuccess;
+}
+void launch_mtail_fwd(hipStream_t s, const LArgs& a) {
+    hipLaunchKernelGGL((k_learner_fwd<kH2, true>), dim3(3 * a.B / kE), dim3(kThreads), kLdsFloats * sizeof(float), s, a);
+}
+void launch_mtail_bwd(hipStream_t s, const LArgs& a) {
+    hipLaunchKernelGGL((k_learner_bwd<kH2, true>), dim3(a.B / kE), dim3(kThreads), bwd_lds_floats(kH2) * sizeof(float), s, a);
+}
+
 }  // namespace learner
 }  // namespace qcart
 
@@ -533,9 +526,6 @@ struct qc_learner {
 
 namespace {
 CreateError g_learner_err;
-
-constexpr double kBeta1 = 0.9, kBeta2 = 0.9995, kEps = 1e-15;   // the defaults: IHO / IQO / QO RL.py:144-145
-constexpr int kCenteredAfter = 10;                               // optimizer.py:9
 
 // tensor indices of layer l (fc1, fc2, fc31, fc41, fc32, fc42): weight, bias, then g | sigma_w, sigma_b
 constexpr int kFirst[6] = {0, 3, 6, 10, 14, 17};

@@ -38,7 +38,7 @@ from typing import Mapping, Optional
 import torch
 
 from . import _lib as L
-from .actor import _layer_tensors, fc2_width
+from .actor import M_CONV, _layer_tensors, fc2_width, measurement_flat_len
 from .replay import _view
 
 LAYERS = ("fc1", "fc2", "fc31", "fc41", "fc32", "fc42")
@@ -220,4 +220,227 @@ class DQNLearner(L.DeviceHandle):
         """Synchronises. Raises QCartError if an update since the last call saw an out-of-range action."""
         s = L.QcLearnerStats()
         self._check(L.lib().qc_learner_stats(self._h, ctypes.byref(s)))
+        return {k: getattr(s, k) for k, _ in L.QcLearnerStats._fields_}
+
+
+M_LEARNER_LAYERS = ("conv1", "conv2", "conv3", "fc1", "fc21", "fc31", "fc22", "fc32")
+_M_KIND = ("plain", "plain", "plain", "plain", "noisy", "noisy", "wn", "wn")
+
+
+def measurement_row_len(read_length: int, read_step_length: int) -> int:
+    """Length of a 'measurements' replay row (qc_record): L + m measurements, K + 1 forces, action, reward."""
+    return read_length + read_step_length + read_length // read_step_length + 3
+
+
+class MeasurementLearner(L.DeviceHandle):
+    """TrainDQN for the inverted harmonic driver's DQN_measurement (the 'measurements' input, RL.py:29-78 and
+    :159-232) with centred LaProp: one update per call on `batch_size` rows of MeasurementRecord
+    (csrc/qcart_mlearner.hip, `qc_mlearner_update`), without leaving the device:
+
+        learner = MeasurementLearner(net.state_dict(), rec.read_length, rec.m, batch_size=512)
+        while training:
+            ...                               # MeasurementRecord.record(rows=...) -> memory.store
+            learner.step(memory)              # obtain_sample -> update -> batch_update
+            learner.push(mactor)              # device-to-device weight push into a MeasurementActor
+
+    conv1..3 and fc1 are plain Conv1d / Linear layers; a state_dict whose convolutions carry a weight_norm (the
+    harmonic driver's Conv1d_weight_normalize stack) is refused. batch_size: a multiple of 128 in [128, 1024]."""
+
+    _prefix = "qc_mlearner"
+
+    def __init__(self, params: Mapping[str, torch.Tensor], read_length: int, read_step_length: int,
+                 batch_size: int = 512, gamma: float = 0.998, lr: float = 4e-4, alive_reward: float = 10.,
+                 failing_reward: float = -1., backup_period: int = 300, target: str = "alive",
+                 betas=(0.9, 0.9995), device: int | str | torch.device = 0, seed: int = 0):
+        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("MeasurementLearner runs on a HIP device only (no CPU fallback)")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if batch_size % 128 != 0 or not 128 <= batch_size <= 1024:
+            raise ValueError("batch_size must be a multiple of 128 in [128, 1024] (FactorizedNoisy's 32-chunk "
+                             "noise branch; the per-row branch of other sizes is not implemented)")
+        if "conv1.weight" not in params or "fc31.u_w" not in params:
+            raise ValueError("params must be a DQN_measurement state_dict (conv1.weight, ..., fc31.u_w)")
+        if read_step_length < 1 or read_length % read_step_length != 0:
+            raise ValueError(f"read_length {read_length} must be a multiple of read_step_length {read_step_length}")
+        if target not in L.TD_TARGETS:
+            raise ValueError(f"target must be one of {sorted(L.TD_TARGETS)}, not {target!r}")
+        self.target = target
+        self.betas = (float(betas[0]), float(betas[1]))
+        for name, b in zip(("beta1", "beta2"), self.betas):
+            if not 0. < b < 1.:
+                raise ValueError(f"{name} (betas) must be in (0, 1), not {b}")
+        self.read_length, self.read_step_length = int(read_length), int(read_step_length)
+        self.n_actions = int(params["fc31.u_w"].shape[0])
+        self.batch_size = int(batch_size)
+        self.flat_len = measurement_flat_len(self.read_length)
+        self.row_len = measurement_row_len(self.read_length, self.read_step_length)
+        p = L.QcMlearnerParams()
+        p.read_length, p.read_step_length = self.read_length, self.read_step_length
+        p.n_actions, p.batch_size = self.n_actions, self.batch_size
+        p.backup_period, p.target_mode = int(backup_period), L.TD_TARGETS[target]
+        p.gamma, p.lr = float(gamma), float(lr)
+        p.alive_reward, p.failing_reward, p.seed = float(alive_reward), float(failing_reward), int(seed)
+        p.beta1, p.beta2 = self.betas
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            torch.cuda.init()
+            self._check(L.lib().qc_mlearner_create(ctypes.byref(p), self.device.index, ctypes.byref(h)))
+        self._h = h
+        self.noise_len = int(L.lib().qc_mlearner_noise_len(h))
+        self.counter = 0
+        self.last_loss = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._keep = []
+        self.load_state_dict(params)
+
+    def _shapes(self):
+        return [(o, i, k) for i, o, k, _ in M_CONV] + [(256, self.flat_len), (256, 256), (self.n_actions, 256),
+                                                       (128, 256), (1, 128)]
+
+    def _layer_array(self, params: Mapping[str, torch.Tensor]):
+        layers = (L.QcDqnLayer * 8)()
+        keep = []
+        for i, (name, shape) in enumerate(zip(M_LEARNER_LAYERS, self._shapes())):
+            if _M_KIND[i] == "plain":
+                if f"{name}.weight" not in params:
+                    raise ValueError(f"{name}.weight is missing: not a DQN_measurement state_dict")
+
+                def t(key):
+                    return params[f"{name}.{key}"].detach().to(device=self.device, dtype=torch.float32).contiguous()
+                g = t("weight_norm").reshape(1) if f"{name}.weight_norm" in params else None
+                ts = (t("weight"), t("bias"), g, None, None)   # a weight_norm is refused by name in the library
+            else:
+                if (_M_KIND[i] == "noisy") != (f"{name}.u_w" in params):
+                    raise ValueError(f"{name}: the learner covers DQN_measurement's fc21 / fc31 FactorizedNoisy and "
+                                     "fc22 / fc32 Linear_weight_normalize only")
+                ts = _layer_tensors(params, name, self.device)
+            if tuple(ts[0].shape) != shape:
+                raise ValueError(f"{name}: weight shape {tuple(ts[0].shape)} != {shape}")
+            keep += ts
+            L.fill_layer(layers[i], ts)
+        return layers, keep
+
+    def load_state_dict(self, params: Mapping[str, torch.Tensor]):
+        """Load the eight layers from a DQN_measurement state_dict (the reference's, or
+        actor.random_dqn_measurement's); resets the optimizer state and the target schedule."""
+        layers, keep = self._layer_array(params)
+        with torch.cuda.device(self.device):
+            self._bind_stream()
+            self._check(L.lib().qc_mlearner_load(self._h, layers))
+        self._keep = keep   # the copies read them on the current stream
+
+    def _tensors(self, layers) -> dict:
+        out = {}
+        for i, (name, shape) in enumerate(zip(M_LEARNER_LAYERS, self._shapes())):
+            ly, o = layers[i], shape[0]
+            n = 1
+            for d in shape:
+                n *= d
+            w = _view(ly.weight, n, torch.float32, self.device).view(*shape)
+            b = _view(ly.bias, o, torch.float32, self.device)
+            if _M_KIND[i] == "noisy":
+                out[f"{name}.u_w"] = w
+                out[f"{name}.sigma_w"] = _view(ly.sigma_w, n, torch.float32, self.device).view(*shape)
+                out[f"{name}.u_b"] = b
+                out[f"{name}.sigma_b"] = _view(ly.sigma_b, o, torch.float32, self.device)
+            else:
+                out[f"{name}.weight"] = w
+                out[f"{name}.bias"] = b
+                if _M_KIND[i] == "wn":
+                    out[f"{name}.weight_norm"] = _view(ly.weight_norm, 1, torch.float32, self.device).view(())
+        return out
+
+    def state_dict(self, target: bool = False) -> dict:
+        """The online (or target) parameters under the reference's key names, as device copies."""
+        layers = (L.QcDqnLayer * 8)()
+        self._check(L.lib().qc_mlearner_layers(self._h, 1 if target else 0, layers))
+        with torch.cuda.device(self.device):
+            return {k: v.clone() for k, v in self._tensors(layers).items()}
+
+    def grads(self) -> dict:
+        """Gradients of the last update under the parameters' key names (weight_norm: dg), as device copies."""
+        layers = (L.QcDqnLayer * 8)()
+        self._check(L.lib().qc_mlearner_grads(self._h, layers))
+        with torch.cuda.device(self.device):
+            return {k: v.clone() for k, v in self._tensors(layers).items()}
+
+    def apply(self, grads: Mapping[str, torch.Tensor]):
+        """One LaProp step on injected gradients (tests)."""
+        layers, keep = self._layer_array(grads)
+        with torch.cuda.device(self.device):
+            self._bind_stream()
+            self._check(L.lib().qc_mlearner_apply(self._h, layers))
+        self._keep = keep
+
+    def set_lr(self, lr: float):
+        self._check(L.lib().qc_mlearner_set_lr(self._h, float(lr)))
+
+    def _rows(self, transitions: torch.Tensor) -> torch.Tensor:
+        if transitions.dim() != 2 or tuple(transitions.shape) != (self.batch_size, self.row_len):
+            raise ValueError(f"transitions must be [{self.batch_size}, {self.row_len}]")
+        return transitions.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def states(self, transitions: torch.Tensor):
+        """(next, prev) [batch_size, 2, read_length]: the states the update assembles from the rows (tests)."""
+        tr = self._rows(transitions)
+        nxt = torch.empty((self.batch_size, 2, self.read_length), dtype=torch.float32, device=self.device)
+        prv = torch.empty_like(nxt)
+        vp = ctypes.c_void_p
+        with torch.cuda.device(self.device):
+            self._bind_stream()
+            self._check(L.lib().qc_mlearner_states(self._h, vp(tr.data_ptr()), vp(nxt.data_ptr()), vp(prv.data_ptr())))
+        return nxt, prv
+
+    def update(self, transitions: torch.Tensor, is_weights: torch.Tensor, noise: Optional[torch.Tensor] = None,
+               counter: Optional[int] = None) -> torch.Tensor:
+        """One update on rows [batch_size, row_len] and IS weights [batch_size]; noise, counter, the return
+        value and the out-of-range-action report as DQNLearner.update."""
+        tr = self._rows(transitions)
+        if is_weights.numel() != self.batch_size:
+            raise ValueError(f"is_weights must be [{self.batch_size}]")
+        w = is_weights.to(device=self.device, dtype=torch.float32).contiguous()
+        nz = None
+        if noise is not None:
+            if tuple(noise.shape) != (32, self.noise_len):
+                raise ValueError(f"noise must be [32, {self.noise_len}]")
+            nz = noise.to(device=self.device, dtype=torch.float32).contiguous()
+        if counter is None:
+            counter = self.counter
+            self.counter += 1
+        ul = torch.empty(self.batch_size, dtype=torch.float32, device=self.device)
+        vp = ctypes.c_void_p
+        with torch.cuda.device(self.device):
+            self._bind_stream()
+            self._check(L.lib().qc_mlearner_update(
+                self._h, vp(tr.data_ptr()), vp(w.data_ptr()), vp(nz.data_ptr()) if nz is not None else None,
+                int(counter), vp(ul.data_ptr()), vp(self.last_loss.data_ptr())))
+        return ul
+
+    def step(self, memory, counter: Optional[int] = None):
+        """TrainDQN.__call__: obtain_sample -> update -> memory.batch_update(tree_idx, unweighted_loss). None
+        while len(memory) < batch_size (RL.py:161)."""
+        smp = memory.obtain_sample(self.batch_size)
+        if smp is None:
+            return None
+        tree_idx, is_weights, transitions = smp
+        ul = self.update(transitions, is_weights, counter=counter)
+        memory.batch_update(tree_idx, ul)
+        return ul
+
+    def push(self, mactor):
+        """Load the online conv1..3, fc1, fc21, fc31 into a MeasurementActor, device to device."""
+        if (mactor.read_length, mactor.n_actions) != (self.read_length, self.n_actions):
+            raise ValueError(f"push: the actor's net (read_length {mactor.read_length}, n_actions {mactor.n_actions}) "
+                             f"is not the learner's (read_length {self.read_length}, n_actions {self.n_actions})")
+        layers = (L.QcDqnLayer * 8)()
+        self._check(L.lib().qc_mlearner_layers(self._h, 0, layers))
+        with torch.cuda.device(self.device):
+            mactor._bind_stream()
+            L.check_mactor(L.lib().qc_mactor_load(mactor._h, layers), mactor._h)
+
+    def stats(self) -> dict:
+        """Synchronises. Raises QCartError if an update since the last call saw an out-of-range action."""
+        s = L.QcLearnerStats()
+        self._check(L.lib().qc_mlearner_stats(self._h, ctypes.byref(s)))
         return {k: getattr(s, k) for k, _ in L.QcLearnerStats._fields_}

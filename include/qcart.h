@@ -501,6 +501,51 @@ int qc_learner_stats(qc_learner* l, qc_learner_stats_t* out);
 int qc_learner_grads(qc_learner* l, qc_dqn_layer out[6]);
 int qc_learner_apply(qc_learner* l, const qc_dqn_layer grads[6]);
 
+/* ---------------------------------------------------------------------------------------------
+ * Device learner of the measurement-input network: one TrainDQN.__call__ update (RL.py:159-232) of the inverted
+ * harmonic driver's DQN_measurement (RL.py:29-78): plain Conv1d(2, 32, 13, /5) -> (32, 64, 11, /4) ->
+ * (64, 64, 9, /4), ReLU each, flatten, Linear(64 T3, 256) + ReLU, fc21 / fc31 FactorizedNoisy, the mean head
+ * fc22 / fc32 Linear_weight_normalize; centred LaProp, fp32 throughout on f32-input MFMA, the loss and the noise
+ * as qc_learner (H2 = 256). A transition is a row of qc_record: K = read_length / read_step_length,
+ *   row = [measurements (read_length + read_step_length, newest first) | forces (K + 1, newest first) | action | reward]
+ * and the states are next[0] = row[0 : L], prev[0] = row[m : m + L], next[1][k m : (k + 1) m] = forces[k],
+ * prev[1][k m : (k + 1) m] = forces[k + 1] (RL.py:180-192). Gradients use no atomics: the same inputs give
+ * bit-identical parameters. All pointers are device pointers; every call is asynchronous on the handle's stream
+ * except qc_mlearner_stats. The weight-normalised convolution stack of the harmonic driver is not implemented:
+ * a conv or fc1 layer with weight_norm is refused by name. */
+typedef struct qc_mlearner qc_mlearner;
+typedef struct qc_mlearner_params {
+    int32_t read_length;           /* L */
+    int32_t read_step_length;      /* m; L % m == 0 */
+    int32_t n_actions;
+    int32_t batch_size;            /* multiple of 128 in [128, 1024] */
+    int32_t backup_period;
+    int32_t target_mode;           /* QC_TD_* */
+    double gamma, lr, alive_reward, failing_reward;
+    double beta1, beta2;           /* LaProp's betas in [0, 1); 0: 0.9 and 0.9995 */
+    uint64_t seed;                 /* Philox key of the in-kernel noise */
+} qc_mlearner_params;
+int qc_mlearner_create(const qc_mlearner_params* p, int device, qc_mlearner** out);
+void qc_mlearner_destroy(qc_mlearner* l);
+const char* qc_mlearner_last_error(const qc_mlearner* l);   /* l may be NULL: last create failure */
+int qc_mlearner_set_stream(qc_mlearner* l, void* stream);
+int qc_mlearner_noise_len(const qc_mlearner* l);            /* per chunk, at H2 = 256: 789 at 21 actions */
+/* layers[8] = conv1, conv2, conv3, fc1, fc21, fc31, fc22, fc32 (conv weights as [out][in * kernel]); resets the
+ * optimizer state and backup_counter */
+int qc_mlearner_load(qc_mlearner* l, const qc_dqn_layer layers[8]);
+/* device pointers to the natural-layout parameters (target != 0: the target network's): qc_mactor_load takes
+ * out[0..5] as they are */
+int qc_mlearner_layers(qc_mlearner* l, int target, qc_dqn_layer out[8]);
+/* as qc_learner_update; transitions [B][L + m + K + 3] */
+int qc_mlearner_update(qc_mlearner* l, const float* transitions, const float* is_weights, const float* noise,
+                       uint64_t counter, float* unweighted_loss, float* loss);
+int qc_mlearner_set_lr(qc_mlearner* l, double lr);
+int qc_mlearner_stats(qc_mlearner* l, qc_learner_stats_t* out);   /* as qc_learner_stats */
+int qc_mlearner_grads(qc_mlearner* l, qc_dqn_layer out[8]);
+int qc_mlearner_apply(qc_mlearner* l, const qc_dqn_layer grads[8]);
+/* tests: the assembled states of a batch, next_out / prev_out [B][2][L] */
+int qc_mlearner_states(qc_mlearner* l, const float* transitions, float* next_out, float* prev_out);
+
 /* ---- batched episode loop: the per-control-step bookkeeping of Control.do_episode --------------------------
  * (IHO/main_parallel.py:242-268, IQO/main_parallel.py:190-221; the cartpoles, 'xp' input) for every env after a
  * step call of one control interval, on the device (BatchedEnv reset="deferred"): pending[e] (in) marks the envs

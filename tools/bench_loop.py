@@ -39,11 +39,9 @@ def main():
     ap.add_argument("--marker", action="store_true",
                     help="wrap the timed steps in a roctx range 'timed' (tools/loop_breakdown.py, rocprofv3 --marker-trace)")
     ap.add_argument("--learn", type=int, default=0,
-                    help="device learner steps (DQNLearner.step: sample(512) -> update -> batch_update) plus one weight "
-                         "push into the actor per control step; 'xp' input only; 0: none (the default)")
+                    help="device learner steps (DQNLearner.step / MeasurementLearner.step: sample(512) -> update -> "
+                         "batch_update) plus one weight push into the actor per control step; 0: none (the default)")
     args = ap.parse_args()
-    if args.learn and args.input != "xp":
-        ap.error("--learn needs --input xp (the learner covers direct_DQN)")
     if args.reset is None:
         args.reset = "deferred" if args.input == "xp" else "immediate"
     B = args.batch
@@ -58,7 +56,13 @@ def main():
         actor = DQNActor({k: v.cuda() for k, v in random_direct_dqn(seed=1).items()}, max_batch=B, seed=2)
         mem = PrioritizedReplay(args.capacity or 7000 * 18 * 100, 2 * 5 + 2, "random", 0.2, device=0, seed=3)
     learner = None
-    if args.learn:
+    if args.learn and meas:
+        from deepreinforcementlearningcontrolofquantumcartpoles_amd.learner import MeasurementLearner
+        rec = env.rec      # the env's MeasurementRecord: its read_length and control-step length m
+        learner = MeasurementLearner(random_dqn_measurement(seed=1), rec.read_length, rec.m, batch_size=512, device=0,
+                                     seed=4)
+        assert learner.row_len == row_len
+    elif args.learn:
         from deepreinforcementlearningcontrolofquantumcartpoles_amd.learner import DQNLearner
         learner = DQNLearner(random_direct_dqn(seed=1), batch_size=512, device=0, seed=4)
     obs = env.reset()

@@ -1,0 +1,119 @@
+#!/usr/bin/env python3
+"""The device measurement learner beside the same update written in torch, on one GPU.
+
+Device path: MeasurementLearner.update (csrc/qcart_mlearner.hip, 28 launches per update). Baseline: the same
+update as torch ops on the same GPU in the same run (tests/mlearner_ref.py's restatement in fp32: F.conv1d /
+F.linear, the chunked NoisyNet noise, the TD loss, autograd, LaProp as per-tensor ops). Both run one fixed batch
+with injected noise at L = 5760, m = 80; per batch size: warmup updates, then `--steps` timed updates between two
+synchronisations (wall clock), best of 3 alternating rounds. Prints one JSON line.
+usage: python tools/bench_mlearner.py [--steps K] [--warmup W]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+from deepreinforcementlearningcontrolofquantumcartpoles_amd.learner import MeasurementLearner  # noqa: E402
+from tests import mlearner_ref as M  # noqa: E402
+
+L, MS = 5760, 80
+PEAK_F32_MFMA = 157.3e12
+
+
+class TorchLearner:
+    """TrainDQN.__call__ + LaProp (centered, betas (0.9, 0.9995)) as torch ops on the device."""
+
+    def __init__(self, params, lr=4e-4, backup_period=300):
+        self.p = {k: v.detach().cuda().float().clone().requires_grad_(True) for k, v in params.items()}
+        self.state = {k: [torch.zeros_like(v), torch.zeros_like(v), torch.zeros_like(v)] for k, v in self.p.items()}
+        self.lr, self.step_count, self.l1, self.l2 = lr, 0, 0.0, 0.0
+        self.backup_period, self.backup_counter, self.target = backup_period, 0, None
+
+    def update(self, tr, w, noise):
+        if self.backup_counter == 0:
+            self.target = {k: v.detach().clone() for k, v in self.p.items()}
+        self.backup_counter = (self.backup_counter + 1) % self.backup_period
+        loss, ul, _ = M.td_loss(self.p, self.target, tr, w, noise, L, MS)
+        loss.backward()
+        b1, b2, lr = 0.9, 0.9995, self.lr
+        self.step_count += 1
+        self.l1 = self.l1 * b1 + (1 - b1) * lr
+        self.l2 = self.l2 * b2 + (1 - b2)
+        step_size = 1.0 / (self.l1 / lr if lr != 0.0 else 1.0)
+        with torch.no_grad():
+            for k, p in self.p.items():
+                g = p.grad
+                e, v, mu = self.state[k]
+                v.mul_(b2).addcmul_(g, g, value=1 - b2)
+                mu.mul_(b2).add_(g, alpha=1 - b2)
+                den = v - mu ** 2 if self.step_count > 10 else v
+                den = den.div(self.l2).sqrt_().add_(1e-15)
+                e.mul_(b1).add_(g / den, alpha=(1 - b1) * lr)
+                p.add_(e, alpha=-step_size)
+                p.grad = None
+        return ul.detach()
+
+
+def timed(fn, warmup, steps):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / steps * 1e3
+
+
+def gemm_flops(B):
+    """FLOPs per update of each GEMM family (2 MACs): forward on 3 B states, backward on B."""
+    t = M.dims(L)
+    fwd = sum(2 * co * ci * k * t[j + 1] for j, (ci, co, k, _) in enumerate(M.CONV)) + 2 * 64 * t[3] * 256
+    dw = sum(2 * co * ci * k * t[j + 1] for j, (ci, co, k, _) in enumerate(M.CONV))
+    dx = sum(2 * co * ci * k * t[j + 1] for j, (ci, co, k, _) in enumerate(M.CONV) if j > 0)
+    return {"forward_3B": 3 * B * fwd, "conv_dw": B * dw, "conv_dx": B * dx, "fc1_t_and_dw": B * 2 * 2 * 64 * t[3] * 256}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--device-only", action="store_true", help="only the device learner (for a kernel trace)")
+    ap.add_argument("--batches", type=int, nargs="+", default=[128, 512])
+    args = ap.parse_args()
+    params = M.random_params(L, seed=5)
+    out = {"metric": "measurement learner ms per update (DQN_measurement, LaProp; device learner vs torch on the same GPU)",
+           "unit": "ms/update", "steps": args.steps, "warmup": args.warmup, "read_length": L, "read_step_length": MS}
+    for B in args.batches:
+        tr, w, nz = (torch.as_tensor(a).cuda() for a in M.make_batch(B, 3, L, MS))
+        dev = MeasurementLearner(params, L, MS, batch_size=B)
+        ref = None if args.device_only else TorchLearner(params)
+        d_ms, t_ms = [], []
+        for _ in range(1 if args.device_only else 3):
+            d_ms.append(timed(lambda: dev.update(tr, w, noise=nz), args.warmup, args.steps))
+            if ref is not None:
+                t_ms.append(timed(lambda: ref.update(tr, w, nz), max(2, args.warmup // 4), max(5, args.steps // 4)))
+        st = dev.stats()
+        out[f"device_ms_B{B}"] = min(d_ms)
+        out[f"device_ms_rounds_B{B}"] = d_ms
+        if t_ms:
+            out[f"torch_ms_B{B}"] = min(t_ms)
+            out[f"torch_ms_rounds_B{B}"] = t_ms
+            out[f"speedup_B{B}"] = min(t_ms) / min(d_ms)
+        fl = gemm_flops(B)
+        out[f"gemm_flops_B{B}"] = fl
+        out[f"update_frac_of_f32_mfma_peak_B{B}"] = sum(fl.values()) / (min(d_ms) * 1e-3) / PEAK_F32_MFMA
+        out["launches_per_update"] = st["launches_per_update"]
+        assert st["nonfinite"] == 0
+        del dev, ref
+    out["value"] = out[f"device_ms_B{args.batches[-1]}"]
+    out["data"] = "synthetic: one fixed batch (tests/mlearner_ref.make_batch), random-initialised DQN_measurement, injected noise"
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
