@@ -9,6 +9,10 @@ TD target of a row with reward r, nsv the target net's value of the online net's
     "alive"        y = gamma nsv + (1 - gamma) alive_reward;  y = 0 where r == failing_reward
     "reward_fail"  y = gamma nsv + (1 - gamma) r;             y = r where r <= failing_reward
     "reward"       y = gamma nsv + (1 - gamma) r
+
+trained_like() moves freshly initialised parameters off the initialisers' special values (weight_norm = ||W||_F,
+u_b = 0, one sigma per layer), and r32_trajectory() measures what fp32 rounding alone costs along a few updates
+with a stale target:  python -m tests.dqn_variants_ref HIDDEN2 TARGET   (or HIDDEN2 N_ACTIONS DATA_LENGTH)
 """
 import numpy as np
 import torch
@@ -16,6 +20,41 @@ import torch
 from tests.learner_ref import CHUNKS, SCALE, LaProp, _wn, f_noise, noisy_linear, to_params  # noqa: F401
 
 TARGETS = ("alive", "reward_fail", "reward")
+
+# The stale-target cases of the four drivers (learner.py's table), shared by tests/test_dqn_trained_cpu.py and
+# tests/test_gpu_dqn_trained.py: parameters trained_like(random_direct_dqn(seed=11, hidden2), 3), B = 128, L = 5.
+#   seeds  the two batches that the updates alternate. The first is the first of 1..8 that meets every bar of
+#          test_dqn_trained_cpu.py's stale-target preconditions, the second the first other seed of 1..8 with
+#          which every row's argmax is clear at all 7 updates of the restatement's own trajectory.
+#   r32    per tensor, the largest max|g32 - g64| / max|g64| over those 7 updates (r32_trajectory: this
+#          restatement in fp32 against fp64 on the CPU); tensors not listed stayed at or below 2.5e-6, where the
+#          gradient bound max(2e-5, 8 r32) is 2e-5.
+DRIVERS = {
+    (256, "alive"): {"betas": (0.9, 0.9995), "seeds": (3, 1), "r32": {
+        "fc1.weight_norm": 9.6e-05, "fc2.weight_norm": 5.9e-05, "fc32.weight": 3.9e-06, "fc32.bias": 3.3e-06,
+        "fc32.weight_norm": 3.9e-06, "fc42.weight": 3.4e-06, "fc42.bias": 3.1e-06, "fc42.weight_norm": 3.7e-06}},
+    (512, "alive"): {"betas": (0.9, 0.9995), "seeds": (1, 4), "r32": {
+        "fc1.weight_norm": 5.8e-06, "fc2.weight": 2.8e-06, "fc2.weight_norm": 6.0e-06, "fc31.u_w": 2.7e-06,
+        "fc31.sigma_w": 2.6e-06, "fc32.weight": 6.9e-06, "fc32.bias": 5.7e-06, "fc32.weight_norm": 1.1e-05,
+        "fc41.sigma_w": 2.7e-06, "fc42.weight": 7.8e-06, "fc42.bias": 5.7e-06, "fc42.weight_norm": 1.1e-05}},
+    (512, "reward_fail"): {"betas": (0.9, 0.9995), "seeds": (1, 2), "r32": {
+        "fc1.weight_norm": 2.6e-06, "fc2.weight": 2.8e-06, "fc2.weight_norm": 3.1e-06, "fc31.u_w": 2.7e-06,
+        "fc32.weight": 4.5e-06, "fc32.bias": 5.4e-06, "fc32.weight_norm": 6.0e-06, "fc42.weight": 5.8e-06,
+        "fc42.bias": 1.7e-05, "fc42.weight_norm": 6.3e-06}},
+    (256, "reward"): {"betas": (0.9, 0.999), "seeds": (1, 4), "r32": {"fc1.weight_norm": 1.0e-05}},
+}
+# The single-update cases at other head widths, (hidden2, n_actions, data_length), target "alive": the batch seed
+# (the first of 1..8 with every row clear and every action present) and r32 of that one update, as above.
+HEADS = {
+    (512, 32, 9): {"seed": 2, "r32": {"fc2.weight": 2.6e-06, "fc32.weight_norm": 2.6e-06}},
+    (256, 9, 14): {"seed": 1, "r32": {}},
+}
+
+
+def grad_bound(r32, name):
+    """The gradient tolerance of one tensor, relative to max|g_ref|: 2e-5 where fp32 rounding alone stays within
+    1/8 of it, else 8x the rounding (test_gpu_dqn_variants.py)."""
+    return max(2e-5, 8 * r32.get(name, 0.0))
 
 
 def noise_len(hidden2, n_actions=21):
@@ -67,6 +106,14 @@ def actor_q(params, obs, noise=None, dtype=torch.float64):
     return _layer(p, "fc41", a3, sl[2], sl[3]).numpy()
 
 
+def actor_inputs(B, length, obs_seed=1, noise_seed=2):
+    """The actor tests' inputs: observations [B, 5] on the scale of the five moments and per-env noise
+    f(randn(B, length)), float32."""
+    obs = (np.random.default_rng(obs_seed).standard_normal((B, 5)) * SCALE).astype(np.float32)
+    noise = f_noise(np.random.default_rng(noise_seed).standard_normal((B, length))).astype(np.float32)
+    return obs, noise
+
+
 def td_target(nsv, r, target, gamma, alive_reward, failing_reward):
     if target == "alive":
         y = nsv * gamma + (1.0 - gamma) * alive_reward
@@ -82,16 +129,20 @@ def td_target(nsv, r, target, gamma, alive_reward, failing_reward):
     return y
 
 
-def td_loss(p, pt, tr, w, noise, target="alive", gamma=0.998, alive_reward=10.0, failing_reward=-1.0):
+def td_loss(p, pt, tr, w, noise, target="alive", gamma=0.998, alive_reward=10.0, failing_reward=-1.0,
+            swap_roles=False):
     """(loss, ul [B], q_next_online [B, A]) of the online parameters p and target parameters pt; p's tensors
-    may require grad. tr, w, noise: tensors of p's dtype."""
+    may require grad. tr, w, noise: tensors of p's dtype. swap_roles: the mistake of exchanging the two nets on
+    the next states (argmax by the target net, value by the online net), for the tests that show it is visible."""
     L = (tr.shape[1] - 2) // 2
     prev, nxt = tr[:, :L], tr[:, L:2 * L]
     act = tr[:, -2].long()
     with torch.no_grad():
-        qn, _ = forward(p, nxt, noise)
+        qn, mn = forward(p, nxt, noise)
         a_star = qn.max(1)[1]
         qt, mt = forward(pt, nxt, noise)
+        if swap_roles:
+            a_star, qt, mt = qt.max(1)[1], qn, mn
         nsv = qt.gather(1, a_star[:, None]).squeeze(1) + mt - qt.mean(1)
         y = td_target(nsv, tr[:, -1], target, gamma, alive_reward, failing_reward)
     q, m = forward(p, prev, noise)
@@ -108,6 +159,30 @@ def loss_and_grads(params, target_params, tr, w, noise, dtype=torch.float64, **k
     loss, ul, qn = td_loss(p, pt, t(tr), t(w), t(noise), **kw)
     loss.backward()
     return (ul.detach().numpy(), float(loss.detach()), {k: v.grad.numpy() for k, v in p.items()}, qn.numpy())
+
+
+def trained_like(params, seed):
+    """A copy of `params` with what an optimizer step destroys of the initialisers' special values: every
+    *.weight_norm times its own factor in [0.7, 1.4] (so g / ||W||_F != 1), every sigma_w / sigma_b element times
+    its own factor in [0.5, 1.5] (no longer one constant per layer), every u_b drawn from U(-0.05, 0.05). Any
+    noisy_layers, either width; the keys are visited in sorted order, so the result depends on (params, seed)
+    alone."""
+    g = torch.Generator().manual_seed(seed)
+
+    def uni(shape, lo, hi):
+        return lo + (hi - lo) * torch.rand(tuple(shape), generator=g, dtype=torch.float64)
+
+    out = {}
+    for k in sorted(params):
+        v = params[k].detach().cpu()
+        if k.endswith(".weight_norm"):
+            v = (v.double() * uni(v.shape, 0.7, 1.4)).to(v.dtype)
+        elif k.endswith(".sigma_w") or k.endswith(".sigma_b"):
+            v = (v.double() * uni(v.shape, 0.5, 1.5)).to(v.dtype)
+        elif k.endswith(".u_b"):
+            v = uni(v.shape, -0.05, 0.05).to(v.dtype)
+        out[k] = v.clone()
+    return {k: out[k] for k in params}
 
 
 def make_batch(B, seed, L=5, n_actions=21, hidden2=256, target="alive", failing_reward=-1.0):
@@ -151,3 +226,63 @@ def q_tol(q):
 def clear_rows(qn):
     """Rows whose argmax of Q_online(next) is not borderline: top-two gap above twice the q tolerance."""
     return top_two_gap(qn) > 2 * q_tol(qn)
+
+
+def trajectory(params, batches, n, lr=4e-4, betas=(0.9, 0.9995), backup_period=3, dtype=torch.float64, **kw):
+    """n updates of the restatement, batch i % len(batches) at update i, the target copied from the online net at
+    every update whose position in the period is 0: [(before, target, batch index)] per update, as float32
+    parameter dicts (what a device learner would hold)."""
+    opt = LaProp(params, lr=lr, betas=betas, dtype=dtype)
+    f32 = lambda d: {k: v.detach().to(torch.float32).clone() for k, v in d.items()}   # noqa: E731
+    out, target, counter = [], None, 0
+    for i in range(n):
+        before = f32(opt.p)
+        if counter == 0:
+            target = before
+        counter = (counter + 1) % backup_period
+        b = i % len(batches)
+        out.append((before, target, b))
+        g = loss_and_grads(before, target, *batches[b], dtype=dtype, **kw)[2]
+        opt.p = to_params(before, dtype)     # each step starts from the float32 parameters, as the device's does
+        opt.step(g)
+    return out
+
+
+def r32_trajectory(hidden2, target, betas=(0.9, 0.9995), n=7, B=128, L=5, pseed=11, tseed=3, batch_seeds=(1, 2),
+                   n_actions=21, **kw):
+    """What fp32 rounding alone costs along the restatement's own n-update trajectory from
+    trained_like(random_direct_dqn(seed=pseed), tseed): per update, ({tensor: max|g32 - g64| / max|g64|},
+    max|ul32 - ul64| as a share of the ul tolerance, all rows clear) of the restatement in fp32 against fp64 on
+    the same (online, target, batch). CPU only."""
+    from deepreinforcementlearningcontrolofquantumcartpoles_amd.actor import random_direct_dqn
+    p0 = trained_like(random_direct_dqn(data_length=L, n_actions=n_actions, seed=pseed, hidden2=hidden2), tseed)
+    batches = [make_batch(B, s, L=L, n_actions=n_actions, hidden2=hidden2, target=target) for s in batch_seeds]
+    rows = []
+    for before, tgt, b in trajectory(p0, batches, n, betas=betas, target=target, **kw):
+        ul64, _, g64, qn = loss_and_grads(before, tgt, *batches[b], target=target)
+        ul32, _, g32, _ = loss_and_grads(before, tgt, *batches[b], dtype=torch.float32, target=target)
+        r = {k: float(np.abs(g32[k] - g64[k]).max() / np.abs(g64[k]).max()) for k in g64}
+        rows.append((r, float(np.abs(ul32 - ul64).max() / (2e-5 * np.abs(ul64).max() + 1e-5)),
+                     bool(clear_rows(qn).all())))
+    return rows
+
+
+def _main(argv):
+    """python -m tests.dqn_variants_ref HIDDEN2 TARGET               a row of DRIVERS (7 updates)
+       python -m tests.dqn_variants_ref HIDDEN2 N_ACTIONS DATA_LENGTH   a row of HEADS (one update)"""
+    if len(argv) == 2:
+        d = DRIVERS[(int(argv[0]), argv[1])]
+        rows = r32_trajectory(int(argv[0]), argv[1], betas=d["betas"], batch_seeds=d["seeds"])
+    else:
+        h2, A, L = (int(a) for a in argv)
+        rows = r32_trajectory(h2, "alive", n=1, L=L, n_actions=A, batch_seeds=(HEADS[(h2, A, L)]["seed"],))
+    for i, (r, u, c) in enumerate(rows):
+        k = max(r, key=r.get)
+        print(f"update {i + 1}: largest r32 {r[k]:.1e} ({k}), losses {u:.2f} of their tolerance, every row clear {c}")
+    worst = {k: max(r[k] for r, _, _ in rows) for k in rows[0][0]}
+    print("per tensor, above 2.5e-6:", {k: float(f"{v:.1e}") for k, v in worst.items() if v > 2.5e-6})
+
+
+if __name__ == "__main__":
+    import sys
+    _main(sys.argv[1:])
