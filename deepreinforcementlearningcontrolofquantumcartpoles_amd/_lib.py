@@ -165,6 +165,7 @@ class QcMlearnerParams(ctypes.Structure):
         ("beta1", ctypes.c_double),
         ("beta2", ctypes.c_double),
         ("seed", ctypes.c_uint64),
+        ("conv_weight_norm", ctypes.c_int32),
     ]
 
 

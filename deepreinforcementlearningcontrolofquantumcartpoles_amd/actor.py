@@ -206,7 +206,9 @@ def measurement_flat_len(read_length: int) -> int:
 
 class MeasurementActor(_ActorHandle):
     """Device-side action selection for B envs with a reference DQN_measurement's parameters (the
-    'measurements' input, IHO/RL.py:29-78): obs = MeasurementRecord.hist [B, 2, read_length]."""
+    'measurements' input, IHO/RL.py:29-78): obs = MeasurementRecord.hist [B, 2, read_length]. A convolution with
+    a `convN.weight_norm` key is the harmonic driver's Conv1d_weight_normalize (HO/RL.py:29-75, layers.py:86-94):
+    it acts on W g / ||W||_F. fc1 is nn.Linear in every driver; a weight_norm on it is refused."""
 
     _prefix = "qc_mactor"
 
@@ -228,7 +230,10 @@ class MeasurementActor(_ActorHandle):
                 w = params[f"{name}.weight"].detach().to(device=self.device, dtype=torch.float32)
                 w = w.reshape(w.shape[0], -1).contiguous()
                 b = params[f"{name}.bias"].detach().to(device=self.device, dtype=torch.float32).contiguous()
-                t = (w, b, None, None, None)
+                g = None
+                if f"{name}.weight_norm" in params:
+                    g = params[f"{name}.weight_norm"].detach().to(device=self.device, dtype=torch.float32).reshape(1)
+                t = (w, b, g, None, None)
             else:
                 t = _layer_tensors(params, name, self.device)
             if tuple(t[0].shape) != shapes[j]:
@@ -243,10 +248,12 @@ class MeasurementActor(_ActorHandle):
 
 
 def random_dqn_measurement(read_length: int = 5760, n_actions: int = 21, seed: int = 0,
-                           device: str | torch.device = "cpu") -> dict:
+                           device: str | torch.device = "cpu", conv_weight_norm: bool = False) -> dict:
     """Random-initialised parameters of the reference DQN_measurement (RL.py:29-78) as a state_dict:
     PyTorch's default Conv1d / Linear initialisers (conv biases zeroed, RL.py:46-48), FactorizedNoisy as
-    in random_direct_dqn, and the unused mean branch fc22 / fc32. Synthetic weights for tests / benches."""
+    in random_direct_dqn, and the unused mean branch fc22 / fc32. conv_weight_norm: the harmonic driver's
+    Conv1d_weight_normalize stack, convN.weight_norm = the initial ||W||_F (layers.py:86-94); the other tensors
+    are the same. Synthetic weights for tests / benches."""
     g = torch.Generator().manual_seed(seed)
 
     def uni(shape, bound):
@@ -274,4 +281,7 @@ def random_dqn_measurement(read_length: int = 5760, n_actions: int = 21, seed: i
     p.update(noisy("fc31", 256, n_actions))
     p.update(linear("fc22", 256, 128))
     p.update(linear("fc32", 128, 1))
+    if conv_weight_norm:
+        for j in (1, 2, 3):
+            p[f"conv{j}.weight_norm"] = p[f"conv{j}.weight"].norm()
     return {k: v.to(device=device, dtype=torch.float32) for k, v in p.items()}

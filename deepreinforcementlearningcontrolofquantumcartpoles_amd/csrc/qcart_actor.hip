@@ -516,8 +516,10 @@ constexpr LayerRule kActorRules[] = {
     {0b1111, states_where([](bool wn, bool sw, bool) { return !sw && !wn; }), "a deterministic layer needs weight_norm"},
 };
 constexpr LayerRule kMactorRules[] = {
-    {0b001111, states_where([](bool wn, bool sw, bool) { return sw || wn; }),
-     "conv1..3 and fc1 are plain Conv1d / Linear layers (no weight_norm, no sigma)"},
+    {0b000111, states_where([](bool, bool sw, bool) { return sw; }),
+     "conv1..3 are Conv1d or Conv1d_weight_normalize layers (no sigma)"},
+    {0b001000, states_where([](bool wn, bool sw, bool) { return sw || wn; }),
+     "fc1 is a plain Linear layer (no weight_norm, no sigma)"},
     {0b111111, kSigmaApart, kSigmaApartText},
     {0b110000, states_where([](bool wn, bool sw, bool) { return !sw && !wn; }),
      "fc21 / fc31: FactorizedNoisy or Linear_weight_normalize"},
@@ -753,7 +755,7 @@ int qc_mactor_flat_len(const qc_mactor* a) { return a ? a->flat : QC_EINVAL; }
 
 int qc_mactor_load(qc_mactor* a, const qc_dqn_layer layers[6]) {
     if (!a || !layers) return QC_EINVAL;
-    if (const int rc = validate_layers(layers, 6, kMactorRules, 3, a->err)) return rc;
+    if (const int rc = validate_layers(layers, 6, kMactorRules, 4, a->err)) return rc;
     const int O[6] = {kC1, kC2, kC3, kH2, kH3, a->p.n_actions};
     const int K[6] = {2 * 13, kC1 * 11, kC2 * 9, a->flat, kH2, kH3};
     Dev g(a->device);

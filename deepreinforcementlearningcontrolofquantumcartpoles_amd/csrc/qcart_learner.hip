@@ -15,7 +15,7 @@
 //                      the stored activations; writes every layer's dY (and eps_out o dY) feature-major
 //   5 k_learner_dw     one wave per 32x32 tile of every dW = dY X^T (K = B, the wave walks the whole batch
 //                      in a fixed order) and the bias gradients (row sums of dY)
-//   6 k_learner_wndot  <G, W> of the four weight-normalised layers (fixed-order tree, fp64)
+//   6 k_learner_wndot  <G, W> of the four weight-normalised layers (fixed-order tree, fp64; one workgroup per layer)
 //   7 k_learner_opt    weight-norm chain rule + LaProp over the flat parameter / state buffers
 //   8 k_learner_prep   ||W||_F, effective weights -> forward and transposed fragments
 // The target network is a copy of the parameters and of the forward fragments (two device-to-device
@@ -348,17 +348,17 @@ __global__ __launch_bounds__(kThreads) void k_learner_dw(const DwJob* __restrict
 // <G, W> over a weight-normalised layer's weight (G = the gradient of the effective weight): fp64, fixed
 // order; tensor ti + 2 is the layer's weight_norm g
 __global__ __launch_bounds__(1024) void k_learner_wndot(const float* __restrict__ P, const float* __restrict__ G,
-                                                        const int4 wt /* tensor index per block */,
+                                                        const WnTensors wt /* tensor index per block */,
                                                         const TensorTable tt, double* __restrict__ dot) {
     __shared__ double part[1024];
-    const int ti = blockIdx.x == 0 ? wt.x : blockIdx.x == 1 ? wt.y : blockIdx.x == 2 ? wt.z : wt.w;
+    const int ti = wt.t[blockIdx.x];
     const Tensor T = tt.t[ti];
     double s = 0.0;
     for (int i = threadIdx.x; i < T.n; i += 1024) s += (double)G[T.off + i] * (double)P[T.off + i];
     s = block_sum(s, part);
     if (threadIdx.x == 0) {
         dot[T.wn] = s;
-        dot[4 + T.wn] = (double)P[tt.t[ti + 2].off];   // g before the step: the optimizer updates it in the same launch as W
+        dot[kMaxWN + T.wn] = (double)P[tt.t[ti + 2].off];   // g before the step: the optimizer updates it in the same launch as W
     }
 }
 
@@ -369,7 +369,7 @@ __global__ __launch_bounds__(256) void k_learner_opt(const OptArgs a, const Tens
     if (a.chain && T.kind) {
         const double n = (double)a.norm[T.wn], d = a.dot[T.wn];
         if (T.kind == 1) {
-            const double g = a.dot[4 + T.wn];
+            const double g = a.dot[kMaxWN + T.wn];
             c1 = (float)(g / n);
             c2 = (float)(d / (n * n));
         } else {
@@ -409,7 +409,7 @@ __global__ __launch_bounds__(1024) void k_learner_prep(const float* __restrict__
     }
     ss = block_sum(ss, part);
     const float sc = J.g_off >= 0 ? wn_scale(P[J.g_off], ss) : 1.f;
-    if (J.mode == 0 && J.wn >= 0 && blockIdx.y == 0 && threadIdx.x == 0) norm[J.wn] = (float)sqrt(ss);
+    if (J.mode != 1 && J.wn >= 0 && blockIdx.y == 0 && threadIdx.x == 0) norm[J.wn] = (float)sqrt(ss);
     float* out = F + J.out_off;
     const int first = blockIdx.y * 1024 + threadIdx.x, stride = kPrepParts * 1024;
     if (J.mode == 2) {
@@ -461,8 +461,8 @@ void launch_loss(hipStream_t s, int target_mode, const LossArgs& a) {
 void launch_dw(hipStream_t s, const DwJob* jobs, const int4* tl, int ntiles, int B) {
     hipLaunchKernelGGL(k_learner_dw, dim3((ntiles + 3) / 4), dim3(kThreads), 0, s, jobs, tl, ntiles, B);
 }
-void launch_wndot(hipStream_t s, int n_layers, const float* P, const float* G, int4 wn_tensors, const TensorTable& tt,
-                  double* dot) {
+void launch_wndot(hipStream_t s, int n_layers, const float* P, const float* G, const WnTensors& wn_tensors,
+                  const TensorTable& tt, double* dot) {
     hipLaunchKernelGGL(k_learner_wndot, dim3(n_layers), dim3(1024), 0, s, P, G, wn_tensors, tt, dot);
 }
 void launch_opt(hipStream_t s, const OptArgs& o, const TensorTable& tt, int nt) {
@@ -521,7 +521,7 @@ struct qc_learner {
     int ntiles = 0;
     PrepJob* d_prep = nullptr;
     int nprep = 0;
-    int4 wn_tensors{};
+    WnTensors wn_tensors{};
 };
 
 namespace {
@@ -615,7 +615,6 @@ int qc_learner_create(const qc_learner_params* p, int device, qc_learner** out) 
     const int K[6] = {L, kH1, w2, kH3, w2, kHM};
     int off = 0, nwn = 0;
     int wn_of[6] = {-1, -1, -1, -1, -1, -1};
-    int wnt[4] = {0, 0, 0, 0};
     auto add = [&](int ti, int n, int kind, int wn, int w_off) {
         l->tt.t[ti] = Tensor{off, n, kind, wn, w_off};
         off += (n + 3) & ~3;
@@ -629,7 +628,7 @@ int qc_learner_create(const qc_learner_params* p, int device, qc_learner** out) 
             add(t0 + 3, O[j], 0, -1, 0);
         } else {
             wn_of[j] = nwn;
-            wnt[nwn] = t0;
+            l->wn_tensors.t[nwn] = t0;
             const int w_off = off;
             add(t0, O[j] * K[j], 1, nwn, w_off);
             add(t0 + 1, O[j], 0, -1, 0);
@@ -638,7 +637,6 @@ int qc_learner_create(const qc_learner_params* p, int device, qc_learner** out) 
         }
     }
     l->np = off;
-    l->wn_tensors = int4{wnt[0], wnt[1], wnt[2], wnt[3]};
 
     // ---- fragment buffer: forward fragments and padded biases, then the transposed fragments
     const int Kp[6] = {l->in_pad, kH1, w2, kH3, w2, kHM};
@@ -693,7 +691,7 @@ int qc_learner_create(const qc_learner_params* p, int device, qc_learner** out) 
                  oR32 = take((size_t)kHM * B), odQ = take((size_t)32 * B), odQe = take((size_t)32 * B),
                  odM = take((size_t)32 * B), odZ3 = take((size_t)kH3 * B), odZ3e = take((size_t)kH3 * B),
                  odZ32 = take((size_t)kHM * B), odZ2 = take((size_t)w2 * B), odZ1 = take((size_t)kH1 * B);
-    const size_t oLoss = take(4), oNorm = take(4);
+    const size_t oLoss = take(4), oNorm = take(kMaxWN);
     l->ws_floats = w;
 
     Dev g(device);
@@ -709,8 +707,8 @@ int qc_learner_create(const qc_learner_params* p, int device, qc_learner** out) 
     if (e == hipSuccess) e = hipMemset(l->FT, 0, (size_t)l->nf_fwd * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(&l->ws, w * sizeof(float));
     if (e == hipSuccess) e = hipMemset(l->ws, 0, w * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&l->d_dot, 8 * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(l->d_dot, 0, 8 * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc(&l->d_dot, 2 * kMaxWN * sizeof(double));
+    if (e == hipSuccess) e = hipMemset(l->d_dot, 0, 2 * kMaxWN * sizeof(double));
     if (e == hipSuccess) e = hipMalloc(&l->d_cnt, 2 * sizeof(int32_t));
     if (e == hipSuccess) e = hipMemset(l->d_cnt, 0, 2 * sizeof(int32_t));
     if (e == hipSuccess) e = hipMalloc(&l->d_prep, prep.size() * sizeof(PrepJob));

@@ -14,7 +14,8 @@ namespace qcart {
 namespace learner {
 
 constexpr int kChunks = 32;        // FactorizedNoisy.forward: n = 32 noise samples per batch (layers.py:58)
-constexpr int kMaxNT = 22;         // parameter tensors: 20 (direct_DQN), 22 (DQN_measurement)
+constexpr int kMaxNT = 25;         // parameter tensors: 20 (direct_DQN), 22 / 25 (DQN_measurement, plain / weight-normalised convolutions)
+constexpr int kMaxWN = 8;          // weight-normalised layers of one net: 4 (direct_DQN), 2 / 5 (DQN_measurement)
 constexpr int kLdsFloats = dqn::kActLdsFloats + dqn::kHM * dqn::kE;   // the actor's plan, then R32 [128][32]
 
 // offsets into the fragment buffer (floats): forward part first (copied to the target), then transposed
@@ -73,11 +74,15 @@ struct Tensor {
 struct TensorTable {
     Tensor t[kMaxNT];
 };
+// the weight tensor of each weight-normalised layer (k_learner_wndot: one workgroup per entry)
+struct WnTensors {
+    int t[kMaxWN];
+};
 
 struct OptArgs {
     float *P, *G, *E, *V, *MU;
-    const double* dot;    // [4] <G, W>, then [4] the layers' g (k_learner_wndot)
-    const float* norm;    // [4] ||W||_F of the parameters the gradients were taken at
+    const double* dot;    // [kMaxWN] <G, W>, then [kMaxWN] the layers' g (k_learner_wndot)
+    const float* norm;    // [kMaxWN] ||W||_F of the parameters the gradients were taken at
     int chain;            // 1: G holds effective-weight gradients: apply the weight-norm chain rule first
     int centered;         // step > 10
     float beta1, beta2, omb2, l2, elr /* (1 - beta1) lr */, step_size /* 1 / (l1 / lr), or 1 */, eps;
@@ -101,8 +106,8 @@ constexpr int kCenteredAfter = 10;                               // optimizer.py
 void launch_noise(hipStream_t s, const float* in, float* out, int noise_len, uint64_t seed, uint64_t counter);
 void launch_loss(hipStream_t s, int target_mode, const LossArgs& a);
 void launch_dw(hipStream_t s, const DwJob* jobs, const int4* tiles, int ntiles, int B);
-void launch_wndot(hipStream_t s, int n_layers, const float* P, const float* G, int4 wn_tensors, const TensorTable& tt,
-                  double* dot);
+void launch_wndot(hipStream_t s, int n_layers, const float* P, const float* G, const WnTensors& wn_tensors,
+                  const TensorTable& tt, double* dot);
 void launch_opt(hipStream_t s, const OptArgs& o, const TensorTable& tt, int nt);
 void launch_prep(hipStream_t s, const float* P, float* F, const PrepJob* jobs, int njobs, float* norm);
 // the measurement network's tail: direct_DQN from fc31 on at H2 = 256, entered with a.h_in (3 B / 32

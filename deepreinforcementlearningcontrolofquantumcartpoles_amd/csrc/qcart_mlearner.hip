@@ -1,6 +1,9 @@
 // qcart_mlearner.hip — the device learner of the measurement-input network: the reference's TrainDQN.__call__
 // (inverted harmonic oscillator/RL.py:159-232) for DQN_measurement (RL.py:29-78) with centred LaProp, one
-// update per call on a batch of B replay rows (qc_record's layout), fp32 throughout.
+// update per call on a batch of B replay rows (qc_record's layout), fp32 throughout. The convolutions are plain
+// Conv1d layers (the inverted harmonic driver's net) or, on a handle created with conv_weight_norm = 1,
+// Conv1d_weight_normalize layers (the harmonic driver's, harmonic oscillator/RL.py:29-75, layers.py:86-94):
+// effective weight W g / ||W||_F with one scalar g per layer.
 //
 // The forward stack is the measurement actor's (k_mconv / k_mtr / k_mfc, qcart_actor.hip); the tail, the loss, the
 // dense weight gradients, the optimizer and the dense fragment preparation are the direct learner's kernels
@@ -28,6 +31,14 @@
 //   27 k_learner_prep      fc1, fc1^T, the tail's fragments
 //   28 k_mlearner_prep     the convolutions' forward and per-phase transposed fragments
 // and two device-to-device copies (parameters, forward fragments) when the target network follows the online one.
+//
+// A weight-normalised handle takes the same 28 launches. Three more jobs of k_learner_prep (27) write each
+// convolution's effective weight W g / ||W||_F in the natural layout (its plain scaled copy, mode 2) and the fp64
+// norm; k_mlearner_prep (28) builds its fragments from those instead of from the parameters, so the forward
+// stack, the transposed convolutions and, through the copy of the forward fragments, the target net all see
+// effective weights. The convolutions' dW (20-23) is then the gradient G of the effective weight:
+// k_learner_wndot (25) takes <G, W> of five layers, and k_learner_opt (26, 25 tensors) applies the chain rule
+// dW = (g / n)(G - <G, W> W / n^2), dg = <G, W> / n as it does for fc22 / fc32.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -244,6 +255,8 @@ __global__ __launch_bounds__(256) void k_mlearner_reduce(const RedJobs J) {
 //   mode 0  forward, the measurement actor's layout (k_actor_prep, split = 1) and the bias padded to tiles * 32
 //   mode 1  transposed, per phase p: the matrix [ci][k = i CO + co] = W[co][ci][p + S i] (0 where p + S i >= KS)
 //           in k-step pairs (2 s, 2 s + 1): [p][ci tile][step][64]
+// Wb + w_off: the weights the fragments are made of, the parameters themselves (Wb = P) or, on a weight-normalised
+// handle, the effective weights k_learner_prep has just written behind the fragments (Wb = F); the biases are P's
 struct ConvPrepJob {
     int w_off, bias_off, out_off, bias_pad_off;
     int CO, CI, KS, S, mode, n;   // n: fragment floats
@@ -251,10 +264,10 @@ struct ConvPrepJob {
 struct ConvPrepJobs {
     ConvPrepJob j[5];
 };
-__global__ __launch_bounds__(256) void k_mlearner_prep(const float* __restrict__ P, float* __restrict__ F,
+__global__ __launch_bounds__(256) void k_mlearner_prep(const float* __restrict__ P, const float* Wb, float* F,
                                                        const ConvPrepJobs jobs) {
     const ConvPrepJob J = jobs.j[blockIdx.y];
-    const float* W = P + J.w_off;
+    const float* W = Wb + J.w_off;
     const int K = J.CI * J.KS;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < J.n; i += gridDim.x * 256) {
         float v = 0.f;
@@ -283,12 +296,12 @@ using namespace qcart::mlearner;
 using namespace qcart::host;
 
 namespace {
-constexpr int kNTm = 22;   // 6 conv, 2 fc1, 4 + 4 noisy, 3 + 3 weight-normalised
+// parameter tensors: 6 conv, 2 fc1, 4 + 4 noisy, 3 + 3 weight-normalised = 22; a weight-normalised convolution
+// stack adds one g per convolution: 25 (qc_mlearner::nt). The layers are conv1, conv2, conv3, fc1, fc21, fc31,
+// fc22, fc32; a layer's tensors are weight, bias, then g | sigma_w, sigma_b (qc_mlearner::first: its first tensor)
 constexpr int kC[3] = {32, 64, 64}, kCI[3] = {2, 32, 64}, kKS[3] = {13, 11, 9}, kS[3] = {5, 4, 4};
-// first tensor of layer l: conv1, conv2, conv3, fc1, fc21, fc31, fc22, fc32
-constexpr int kFirst[8] = {0, 2, 4, 6, 8, 12, 16, 19};
 constexpr bool kNoisy[8] = {false, false, false, false, true, true, false, false};
-constexpr bool kWnorm[8] = {false, false, false, false, false, false, true, true};
+constexpr bool kWnormTail[8] = {false, false, false, false, false, false, true, true};
 const char* const kName[8] = {"conv1", "conv2", "conv3", "fc1", "fc21", "fc31", "fc22", "fc32"};
 int conv_out(int n, int k, int s) { return (n - (k - 1) + (s - 1)) / s; }   // calculate_next_layer_dim (RL.py:49-50)
 }  // namespace
@@ -308,8 +321,12 @@ struct qc_mlearner {
     int backup_counter = 0;
     double lr = 0, l1 = 0, l2 = 0;
     int launches = 0;
+    bool cwn = false;            // weight-normalised convolutions (qc_mlearner_params::conv_weight_norm)
+    bool wnorm[8]{};             // layer l carries a weight_norm: fc22, fc32, and conv1..3 if cwn
+    int first[8]{}, nt = 0, nwn = 0;   // layer l's first tensor; tensors; weight-normalised layers
     TensorTable tt{};
     int np = 0, nf = 0, nf_fwd = 0;
+    int weff[3] = {0, 0, 0};     // cwn: the convolutions' effective weights [CO][CI KS], behind the fragments in F
     int u8[8]{}, s8[8]{}, ub8[8]{}, sb8[8]{};   // forward fragments / padded biases of the 8 layers
     int tfc1 = 0, tconv[3] = {0, 0, 0};         // fc1^T; conv2^T, conv3^T per-phase fragments (index 1, 2)
     float *P = nullptr, *PT = nullptr, *G = nullptr, *E = nullptr, *V = nullptr, *MU = nullptr;
@@ -331,7 +348,7 @@ struct qc_mlearner {
     ConvPrepJobs cprep{};
     int cprep_blocks = 0;
     RedJobs red{};
-    int4 wn_tensors{};
+    WnTensors wn_tensors{};
     std::vector<void*> allocs;
 };
 
@@ -340,8 +357,8 @@ CreateError g_mlearner_err;
 
 void layer_views(const qc_mlearner* l, const float* base, qc_dqn_layer out[8]) {
     for (int j = 0; j < 8; ++j) {
-        const Tensor* T = &l->tt.t[kFirst[j]];
-        out[j] = qc_dqn_layer{base + T[0].off, base + T[1].off, kWnorm[j] ? base + T[2].off : nullptr,
+        const Tensor* T = &l->tt.t[l->first[j]];
+        out[j] = qc_dqn_layer{base + T[0].off, base + T[1].off, l->wnorm[j] ? base + T[2].off : nullptr,
                               kNoisy[j] ? base + T[2].off : nullptr, kNoisy[j] ? base + T[3].off : nullptr};
     }
 }
@@ -361,7 +378,8 @@ hipError_t dalloc(qc_mlearner* l, T** q, size_t n) {
 }
 
 void launch_conv_prep(qc_mlearner* l) {
-    hipLaunchKernelGGL(k_mlearner_prep, dim3(l->cprep_blocks, 5), dim3(256), 0, l->stream, l->P, l->F, l->cprep);
+    hipLaunchKernelGGL(k_mlearner_prep, dim3(l->cprep_blocks, 5), dim3(256), 0, l->stream, l->P,
+                       l->cwn ? l->F : l->P, l->F, l->cprep);
 }
 
 // optimizer step + fragment preparation (the tail of an update, and qc_mlearner_apply): 3 launches
@@ -382,7 +400,7 @@ void optimizer_and_prep(qc_mlearner* l, int chain) {
     o.elr = (float)((1 - l->b1) * l->lr);
     o.step_size = (float)(l->lr != 0. ? 1. / (l->l1 / l->lr) : 1.);
     o.eps = (float)kEps;
-    launch_opt(l->stream, o, l->tt, kNTm);
+    launch_opt(l->stream, o, l->tt, l->nt);
     launch_prep(l->stream, l->P, l->F, l->d_prep, l->nprep, l->d_norm);
     launch_conv_prep(l);
 }
@@ -430,6 +448,8 @@ int qc_mlearner_create(const qc_mlearner_params* p, int device, qc_mlearner** ou
         return fail("target_mode must be QC_TD_ALIVE, QC_TD_REWARD_FAIL or QC_TD_REWARD", QC_EINVAL);
     if (!(p->beta1 >= 0. && p->beta1 < 1.)) return fail("beta1 must be in [0, 1) (0: 0.9)", QC_EINVAL);
     if (!(p->beta2 >= 0. && p->beta2 < 1.)) return fail("beta2 must be in [0, 1) (0: 0.9995)", QC_EINVAL);
+    if (p->conv_weight_norm != 0 && p->conv_weight_norm != 1)
+        return fail("conv_weight_norm must be 0 (plain Conv1d) or 1 (Conv1d_weight_normalize on conv1..3)", QC_EINVAL);
     if ((uint64_t)(64 * T3) * (uint64_t)(3 * p->batch_size) * sizeof(float) >= (1ull << 32))   // 32-bit buffer offsets
         return fail("read_length too large: fc1's operand [64 T3][3 batch_size] must stay below 4 GiB", QC_EINVAL);
     if (const int rc = check_device(device, g_mlearner_err, "the learner")) return rc;
@@ -456,23 +476,26 @@ int qc_mlearner_create(const qc_mlearner_params* p, int device, qc_mlearner** ou
     // ---- parameter tensors (offsets in multiples of 4 floats)
     const int O[8] = {kC[0], kC[1], kC[2], kH2, kH3, A, kHM, 1};
     const int Kin[8] = {kCI[0] * kKS[0], kCI[1] * kKS[1], kCI[2] * kKS[2], flat, kH2, kH3, kH2, kHM};
-    int off = 0, nwn = 0;
-    int wn_of[8], wnt[4] = {0, 0, 0, 0};
+    l->cwn = p->conv_weight_norm == 1;
+    int off = 0, nwn = 0, nt = 0;
+    int wn_of[8];
     auto add = [&](int ti, int n, int kind, int wn, int w_off) {
         l->tt.t[ti] = Tensor{off, n, kind, wn, w_off};
         off += (n + 3) & ~3;
     };
     for (int j = 0; j < 8; ++j) {
-        const int t0 = kFirst[j];
+        const int t0 = l->first[j] = nt;
+        l->wnorm[j] = kWnormTail[j] || (l->cwn && j < 3);
+        nt += kNoisy[j] ? 4 : l->wnorm[j] ? 3 : 2;
         wn_of[j] = -1;
         if (kNoisy[j]) {
             add(t0, O[j] * Kin[j], 0, -1, 0);
             add(t0 + 1, O[j], 0, -1, 0);
             add(t0 + 2, O[j] * Kin[j], 0, -1, 0);
             add(t0 + 3, O[j], 0, -1, 0);
-        } else if (kWnorm[j]) {
+        } else if (l->wnorm[j]) {
             wn_of[j] = nwn;
-            wnt[nwn] = t0;
+            l->wn_tensors.t[nwn] = t0;
             const int w_off = off;
             add(t0, O[j] * Kin[j], 1, nwn, w_off);
             add(t0 + 1, O[j], 0, -1, 0);
@@ -484,7 +507,9 @@ int qc_mlearner_create(const qc_mlearner_params* p, int device, qc_mlearner** ou
         }
     }
     l->np = off;
-    l->wn_tensors = int4{wnt[0], wnt[1], wnt[2], wnt[3]};
+    l->nt = nt;
+    l->nwn = nwn;
+    const int* first = l->first;
 
     // ---- fragment buffer: the forward fragments (the measurement actor's layout; copied to the target), then
     // the transposed ones
@@ -513,19 +538,24 @@ int qc_mlearner_create(const qc_mlearner_params* p, int device, qc_mlearner** ou
         l->tconv[j] = fo;
         fo += cfrag_n[j];
     }
+    if (l->cwn)
+        for (int j = 0; j < 3; ++j) {
+            l->weff[j] = fo;
+            fo += (kC[j] * Kin[j] + 3) & ~3;
+        }
     l->nf = fo;
 
     std::vector<PrepJob> prep;
     for (int j = 3; j < 8; ++j) {
-        const Tensor* T = &l->tt.t[kFirst[j]];
-        const int g_off = kWnorm[j] ? T[2].off : -1;
+        const Tensor* T = &l->tt.t[first[j]];
+        const int g_off = l->wnorm[j] ? T[2].off : -1;
         prep.push_back(PrepJob{T[0].off, g_off, wn_of[j], O[j], Kin[j], 0, Kin[j], l->u8[j], T[1].off, l->ub8[j]});
         if (kNoisy[j])
             prep.push_back(PrepJob{T[2].off, -1, -1, O[j], Kin[j], 0, Kin[j], l->s8[j], T[3].off, l->sb8[j]});
     }
     auto tjob = [&](int j, int sigma, int kpad, int out_off) {
-        const Tensor* T = &l->tt.t[kFirst[j]];
-        prep.push_back(PrepJob{T[sigma ? 2 : 0].off, kWnorm[j] ? T[2].off : -1, -1, O[j], Kin[j], 1, kpad, out_off, -1, -1});
+        const Tensor* T = &l->tt.t[first[j]];
+        prep.push_back(PrepJob{T[sigma ? 2 : 0].off, l->wnorm[j] ? T[2].off : -1, -1, O[j], Kin[j], 1, kpad, out_off, -1, -1});
     };
     tjob(3, 0, kH2, l->tfc1);
     tjob(4, 0, kH3, f.t31u);
@@ -533,17 +563,25 @@ int qc_mlearner_create(const qc_mlearner_params* p, int device, qc_mlearner** ou
     tjob(5, 0, 32, f.t41u);
     tjob(5, 1, 32, f.t41s);
     tjob(6, 0, kHM, f.t32);
-    prep.push_back(PrepJob{l->tt.t[19].off, l->tt.t[21].off, -1, 1, kHM, 2, kHM, f.w42, -1, -1});
+    prep.push_back(PrepJob{l->tt.t[first[7]].off, l->tt.t[first[7] + 2].off, -1, 1, kHM, 2, kHM, f.w42, -1, -1});
+    // weight-normalised convolutions: the effective weights in the natural layout (and the norms for the optimizer);
+    // k_mlearner_prep, launched after k_learner_prep, makes the fragments from them
+    if (l->cwn)
+        for (int j = 0; j < 3; ++j) {
+            const Tensor* T = &l->tt.t[first[j]];
+            prep.push_back(PrepJob{T[0].off, T[2].off, wn_of[j], kC[j], Kin[j], 2, Kin[j], l->weff[j], -1, -1});
+        }
     l->nprep = (int)prep.size();
     int cmax = 0;
+    auto conv_w = [&](int j) { return l->cwn ? l->weff[j] : l->tt.t[first[j]].off; };   // offset from k_mlearner_prep's Wb
     for (int j = 0; j < 3; ++j) {
         const int n = tiles(kC[j]) * (Kin[j] / 2) * 64;
-        l->cprep.j[j] = ConvPrepJob{l->tt.t[kFirst[j]].off, l->tt.t[kFirst[j] + 1].off, l->u8[j], l->ub8[j],
+        l->cprep.j[j] = ConvPrepJob{conv_w(j), l->tt.t[first[j] + 1].off, l->u8[j], l->ub8[j],
                                     kC[j], kCI[j], kKS[j], kS[j], 0, n};
         cmax = std::max(cmax, n);
     }
     for (int j = 1; j < 3; ++j) {
-        l->cprep.j[2 + j] = ConvPrepJob{l->tt.t[kFirst[j]].off, -1, l->tconv[j], -1, kC[j], kCI[j], kKS[j], kS[j], 1,
+        l->cprep.j[2 + j] = ConvPrepJob{conv_w(j), -1, l->tconv[j], -1, kC[j], kCI[j], kKS[j], kS[j], 1,
                                         cfrag_n[j]};
         cmax = std::max(cmax, cfrag_n[j]);
     }
@@ -568,7 +606,7 @@ int qc_mlearner_create(const qc_mlearner_params* p, int device, qc_mlearner** ou
     const size_t oH2 = take(kH2 * Bs), oH2e = take(kH2 * Bs), oA3 = take(kH3 * Bs), oA3e = take(kH3 * Bs),
                  oR32 = take(kHM * Bs), odQ = take(32 * Bs), odQe = take(32 * Bs), odM = take(32 * Bs),
                  odZ3 = take(kH3 * Bs), odZ3e = take(kH3 * Bs), odZ32 = take(kHM * Bs), odZ2 = take(kH2 * Bs);
-    const size_t oLoss = take(4), oNorm = take(4);
+    const size_t oLoss = take(4), oNorm = take(kMaxWN);
     const size_t oX = take(2 * Bs * 2 * L);
     size_t oy[4] = {0, 0, 0, 0}, ody[4] = {0, 0, 0, 0}, opart[3], opartb[3];
     for (int j = 1; j <= 3; ++j) oy[j] = take(3 * Bs * kC[j - 1] * l->T[j]);
@@ -586,7 +624,7 @@ int qc_mlearner_create(const qc_mlearner_params* p, int device, qc_mlearner** ou
     if (e == hipSuccess) e = dalloc(l, &l->F, (size_t)l->nf);
     if (e == hipSuccess) e = dalloc(l, &l->FT, (size_t)l->nf_fwd);
     if (e == hipSuccess) e = dalloc(l, &l->ws, w);
-    if (e == hipSuccess) e = dalloc(l, &l->d_dot, 8);
+    if (e == hipSuccess) e = dalloc(l, &l->d_dot, 2 * kMaxWN);
     if (e == hipSuccess) e = dalloc(l, &l->d_cnt, 2);
     if (e == hipSuccess) e = dalloc(l, &l->d_prep, prep.size());
     if (e == hipSuccess) e = hipMemcpy(l->d_prep, prep.data(), prep.size() * sizeof(PrepJob), hipMemcpyHostToDevice);
@@ -623,8 +661,8 @@ int qc_mlearner_create(const qc_mlearner_params* p, int device, qc_mlearner** ou
     }
     int blk = 0;
     for (int j = 0; j < 3; ++j) {
-        l->red.j[2 * j] = RedJob{l->part[j], gt(kFirst[j]), kC[j] * Kin[j], l->nchunks[j]};
-        l->red.j[2 * j + 1] = RedJob{l->partb[j], gt(kFirst[j] + 1), kC[j], l->nchunks[j]};
+        l->red.j[2 * j] = RedJob{l->part[j], gt(first[j]), kC[j] * Kin[j], l->nchunks[j]};
+        l->red.j[2 * j + 1] = RedJob{l->partb[j], gt(first[j] + 1), kC[j], l->nchunks[j]};
         for (int q = 0; q < 2; ++q) {
             l->red.first_block[2 * j + q] = blk;
             blk += (l->red.j[2 * j + q].n + 31) / 32;
@@ -633,11 +671,12 @@ int qc_mlearner_create(const qc_mlearner_params* p, int device, qc_mlearner** ou
     l->red.first_block[6] = blk;
 
     // ---- the dense dW jobs and their tiles (dY, X, gradient tensor, bias gradient tensor)
+    const int t1 = first[3], t21 = first[4], t31 = first[5], t22 = first[6], t32 = first[7];
     const DwJob jobs[7] = {
-        {k.dZ2, l->y3p, gt(6), gt(7), kH2, flat},   {k.dZ3, k.H2, gt(8), gt(9), kH3, kH2},
-        {k.dZ3e, k.H2e, gt(10), gt(11), kH3, kH2},  {k.dQ, k.A3, gt(12), gt(13), A, kH3},
-        {k.dQe, k.A3e, gt(14), gt(15), A, kH3},     {k.dZ32, k.H2, gt(16), gt(17), kHM, kH2},
-        {k.dM, k.R32, gt(19), gt(20), 1, kHM},
+        {k.dZ2, l->y3p, gt(t1), gt(t1 + 1), kH2, flat},        {k.dZ3, k.H2, gt(t21), gt(t21 + 1), kH3, kH2},
+        {k.dZ3e, k.H2e, gt(t21 + 2), gt(t21 + 3), kH3, kH2},   {k.dQ, k.A3, gt(t31), gt(t31 + 1), A, kH3},
+        {k.dQe, k.A3e, gt(t31 + 2), gt(t31 + 3), A, kH3},      {k.dZ32, k.H2, gt(t22), gt(t22 + 1), kHM, kH2},
+        {k.dM, k.R32, gt(t32), gt(t32 + 1), 1, kHM},
     };
     std::vector<int4> tl;
     for (int j = 0; j < 7; ++j)
@@ -685,10 +724,19 @@ int qc_mlearner_load(qc_mlearner* l, const qc_dqn_layer layers[8]) {
             l->err = std::string(kName[j]) + ": weight and bias are required";
             return QC_EINVAL;
         }
-        if (j < 4 && Y.weight_norm) {
-            l->err = std::string(kName[j]) + " carries a weight_norm: the weight-normalised convolution stack "
-                     "(Conv1d_weight_normalize, the harmonic driver's) is not implemented; conv1..3 and fc1 are "
-                     "plain Conv1d / Linear layers";
+        if (j == 3 && Y.weight_norm) {
+            l->err = "fc1 carries a weight_norm: fc1 is a plain Linear layer in every driver";
+            return QC_EINVAL;
+        }
+        if (j < 3 && !l->cwn && Y.weight_norm) {
+            l->err = std::string(kName[j]) + " carries a weight_norm, but the handle was created with "
+                     "conv_weight_norm = 0: conv1..3 are plain Conv1d layers (Conv1d_weight_normalize, the harmonic "
+                     "driver's stack, needs conv_weight_norm = 1 and a weight_norm on all three)";
+            return QC_EINVAL;
+        }
+        if (j < 3 && l->cwn && !Y.weight_norm) {
+            l->err = std::string(kName[j]) + " has no weight_norm, but the handle was created with "
+                     "conv_weight_norm = 1: conv1..3 are Conv1d_weight_normalize layers";
             return QC_EINVAL;
         }
         if (j < 4 && (Y.sigma_w || Y.sigma_b)) {
@@ -699,7 +747,7 @@ int qc_mlearner_load(qc_mlearner* l, const qc_dqn_layer layers[8]) {
             l->err = std::string(kName[j]) + " must be a FactorizedNoisy layer (sigma_w and sigma_b, no weight_norm)";
             return QC_EINVAL;
         }
-        if (kWnorm[j] && (!Y.weight_norm || Y.sigma_w || Y.sigma_b)) {
+        if (kWnormTail[j] && (!Y.weight_norm || Y.sigma_w || Y.sigma_b)) {
             l->err = std::string(kName[j]) + " must be a Linear_weight_normalize layer (weight_norm, no sigma)";
             return QC_EINVAL;
         }
@@ -713,13 +761,13 @@ int qc_mlearner_load(qc_mlearner* l, const qc_dqn_layer layers[8]) {
     };
     for (int j = 0; j < 8; ++j) {
         const qc_dqn_layer& Y = layers[j];
-        put(kFirst[j], Y.weight);
-        put(kFirst[j] + 1, Y.bias);
+        put(l->first[j], Y.weight);
+        put(l->first[j] + 1, Y.bias);
         if (kNoisy[j]) {
-            put(kFirst[j] + 2, Y.sigma_w);
-            put(kFirst[j] + 3, Y.sigma_b);
-        } else if (kWnorm[j]) {
-            put(kFirst[j] + 2, Y.weight_norm);
+            put(l->first[j] + 2, Y.sigma_w);
+            put(l->first[j] + 3, Y.sigma_b);
+        } else if (l->wnorm[j]) {
+            put(l->first[j] + 2, Y.weight_norm);
         }
     }
     const size_t pb = (size_t)l->np * sizeof(float);
@@ -846,7 +894,7 @@ int qc_mlearner_update(qc_mlearner* l, const float* transitions, const float* is
     launch_convdw<2, 32, 13, 5>(l, 0);
     hipLaunchKernelGGL(k_mlearner_reduce, dim3(l->red.first_block[6]), dim3(256), 0, s, l->red);
     launch_dw(s, l->d_dwjobs, l->d_tiles, l->ntiles, B);
-    launch_wndot(s, 2, l->P, l->G, l->wn_tensors, l->tt, l->d_dot);
+    launch_wndot(s, l->nwn, l->P, l->G, l->wn_tensors, l->tt, l->d_dot);
     optimizer_and_prep(l, 1);
     launches += 28;
     const hipError_t e = hipGetLastError();
@@ -869,13 +917,13 @@ int qc_mlearner_apply(qc_mlearner* l, const qc_dqn_layer grads[8]) {
     };
     for (int j = 0; j < 8 && e == hipSuccess; ++j) {
         const qc_dqn_layer& Y = grads[j];
-        put(kFirst[j], Y.weight);
-        put(kFirst[j] + 1, Y.bias);
+        put(l->first[j], Y.weight);
+        put(l->first[j] + 1, Y.bias);
         if (kNoisy[j]) {
-            put(kFirst[j] + 2, Y.sigma_w);
-            put(kFirst[j] + 3, Y.sigma_b);
-        } else if (kWnorm[j]) {
-            put(kFirst[j] + 2, Y.weight_norm);
+            put(l->first[j] + 2, Y.sigma_w);
+            put(l->first[j] + 3, Y.sigma_b);
+        } else if (l->wnorm[j]) {
+            put(l->first[j] + 2, Y.weight_norm);
         }
     }
     if (e == hipErrorInvalidValue) return QC_EINVAL;

@@ -224,7 +224,7 @@ class DQNLearner(L.DeviceHandle):
 
 
 M_LEARNER_LAYERS = ("conv1", "conv2", "conv3", "fc1", "fc21", "fc31", "fc22", "fc32")
-_M_KIND = ("plain", "plain", "plain", "plain", "noisy", "noisy", "wn", "wn")
+_M_KIND = ("conv", "conv", "conv", "plain", "noisy", "noisy", "wn", "wn")   # conv: plain, or weight-normalised
 
 
 def measurement_row_len(read_length: int, read_step_length: int) -> int:
@@ -233,9 +233,9 @@ def measurement_row_len(read_length: int, read_step_length: int) -> int:
 
 
 class MeasurementLearner(L.DeviceHandle):
-    """TrainDQN for the inverted harmonic driver's DQN_measurement (the 'measurements' input, RL.py:29-78 and
-    :159-232) with centred LaProp: one update per call on `batch_size` rows of MeasurementRecord
-    (csrc/qcart_mlearner.hip, `qc_mlearner_update`), without leaving the device:
+    """TrainDQN for DQN_measurement (the 'measurements' input, RL.py:29-78 and :159-232) with centred LaProp: one
+    update per call on `batch_size` rows of MeasurementRecord (csrc/qcart_mlearner.hip, `qc_mlearner_update`),
+    without leaving the device:
 
         learner = MeasurementLearner(net.state_dict(), rec.read_length, rec.m, batch_size=512)
         while training:
@@ -243,8 +243,17 @@ class MeasurementLearner(L.DeviceHandle):
             learner.step(memory)              # obtain_sample -> update -> batch_update
             learner.push(mactor)              # device-to-device weight push into a MeasurementActor
 
-    conv1..3 and fc1 are plain Conv1d / Linear layers; a state_dict whose convolutions carry a weight_norm (the
-    harmonic driver's Conv1d_weight_normalize stack) is refused. batch_size: a multiple of 128 in [128, 1024]."""
+    The two drivers that train this net differ in the convolutions, the TD target, LaProp's betas and the geometry:
+
+        driver               conv1..3                   target     betas            read_length, m
+        inverted harmonic    Conv1d                     "alive"    (0.9, 0.9995)    5760, 80
+        harmonic             Conv1d_weight_normalize    "reward"   (0.9, 0.999)     4320, 80
+
+    The convolutions are taken from the state_dict: with a `convN.weight_norm` on all three the handle is a
+    weight-normalised one (`conv_weight_norm`; effective weight W g / ||W||_F, 25 parameter tensors instead of 22,
+    the three g learned through the chain rule), with none a plain one. A state_dict with some of the three lands
+    on a plain handle, which refuses it naming the layer; fc1 is nn.Linear in both drivers and a weight_norm on it
+    is refused. batch_size: a multiple of 128 in [128, 1024]."""
 
     _prefix = "qc_mlearner"
 
@@ -274,6 +283,7 @@ class MeasurementLearner(L.DeviceHandle):
         self.read_length, self.read_step_length = int(read_length), int(read_step_length)
         self.n_actions = int(params["fc31.u_w"].shape[0])
         self.batch_size = int(batch_size)
+        self.conv_weight_norm = all(f"conv{j}.weight_norm" in params for j in (1, 2, 3))
         self.flat_len = measurement_flat_len(self.read_length)
         self.row_len = measurement_row_len(self.read_length, self.read_step_length)
         p = L.QcMlearnerParams()
@@ -283,6 +293,7 @@ class MeasurementLearner(L.DeviceHandle):
         p.gamma, p.lr = float(gamma), float(lr)
         p.alive_reward, p.failing_reward, p.seed = float(alive_reward), float(failing_reward), int(seed)
         p.beta1, p.beta2 = self.betas
+        p.conv_weight_norm = 1 if self.conv_weight_norm else 0
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             torch.cuda.init()
@@ -302,14 +313,15 @@ class MeasurementLearner(L.DeviceHandle):
         layers = (L.QcDqnLayer * 8)()
         keep = []
         for i, (name, shape) in enumerate(zip(M_LEARNER_LAYERS, self._shapes())):
-            if _M_KIND[i] == "plain":
+            if _M_KIND[i] in ("conv", "plain"):
                 if f"{name}.weight" not in params:
                     raise ValueError(f"{name}.weight is missing: not a DQN_measurement state_dict")
 
                 def t(key):
                     return params[f"{name}.{key}"].detach().to(device=self.device, dtype=torch.float32).contiguous()
                 g = t("weight_norm").reshape(1) if f"{name}.weight_norm" in params else None
-                ts = (t("weight"), t("bias"), g, None, None)   # a weight_norm is refused by name in the library
+                # the library decides: a weight_norm the handle has no use for, or a missing one, is refused by name
+                ts = (t("weight"), t("bias"), g, None, None)
             else:
                 if (_M_KIND[i] == "noisy") != (f"{name}.u_w" in params):
                     raise ValueError(f"{name}: the learner covers DQN_measurement's fc21 / fc31 FactorizedNoisy and "
@@ -323,7 +335,8 @@ class MeasurementLearner(L.DeviceHandle):
 
     def load_state_dict(self, params: Mapping[str, torch.Tensor]):
         """Load the eight layers from a DQN_measurement state_dict (the reference's, or
-        actor.random_dqn_measurement's); resets the optimizer state and the target schedule."""
+        actor.random_dqn_measurement's) of the handle's kind of convolutions; resets the optimizer state and the
+        target schedule."""
         layers, keep = self._layer_array(params)
         with torch.cuda.device(self.device):
             self._bind_stream()
@@ -347,7 +360,7 @@ class MeasurementLearner(L.DeviceHandle):
             else:
                 out[f"{name}.weight"] = w
                 out[f"{name}.bias"] = b
-                if _M_KIND[i] == "wn":
+                if _M_KIND[i] == "wn" or (_M_KIND[i] == "conv" and self.conv_weight_norm):
                     out[f"{name}.weight_norm"] = _view(ly.weight_norm, 1, torch.float32, self.device).view(())
         return out
 

@@ -348,7 +348,8 @@ int qc_actor_act(qc_actor* a, int64_t B, int64_t env_offset, const float* obs, i
 /* The measurement-input actor (SURVEY §8f rank 1 for args.input == 'measurements'): DQN_measurement
  * (inverted harmonic oscillator/RL.py:29-78) for B envs: conv1 Conv1d(2, 32, 13, stride 5), conv2
  * Conv1d(32, 64, 11, 4), conv3 Conv1d(64, 64, 9, 4) with ReLU, flatten, fc1 Linear(64 T3, 256) + ReLU,
- * fc21 FactorizedNoisy(256, 256) + ReLU, fc31 FactorizedNoisy(256, n_actions) -> argmax, epsilon-greedy.
+ * fc21 FactorizedNoisy(256, 256) + ReLU, fc31 FactorizedNoisy(256, n_actions) -> argmax, epsilon-greedy;
+ * the harmonic driver's net is the same with weight-normalised convolutions (qc_mactor_load).
  * The convolutions run as implicit GEMMs on f32 MFMA over env chunks; the noise layout and the
  * epsilon-greedy draw are qc_actor's (noise_len = 789 at 21 actions). */
 typedef struct qc_mdqn_params {
@@ -365,8 +366,11 @@ const char* qc_mactor_last_error(const qc_mactor* a);
 int qc_mactor_set_stream(qc_mactor* a, void* stream);
 int qc_mactor_noise_len(const qc_mactor* a);
 int qc_mactor_flat_len(const qc_mactor* a);   /* 64 * T3, fc1's input length */
-/* layers[6] = conv1, conv2, conv3, fc1 (weight [out][in(*kernel)], bias; weight_norm = sigma = NULL),
- * fc21, fc31 (FactorizedNoisy u_w/u_b/sigma_w/sigma_b, or Linear_weight_normalize) — the state_dict */
+/* layers[6] = conv1, conv2, conv3, fc1 (weight [out][in(*kernel)], bias; sigma = NULL), fc21, fc31
+ * (FactorizedNoisy u_w/u_b/sigma_w/sigma_b, or Linear_weight_normalize) — the state_dict. A convolution whose
+ * weight_norm is not NULL is a Conv1d_weight_normalize layer (the harmonic driver's stack, harmonic
+ * oscillator/RL.py:29-75, layers.py:86-94): its effective weight is W g / ||W||_F with the one scalar g, each of
+ * conv1..3 decided by its own pointer. fc1 is nn.Linear in every driver: a weight_norm on it is refused. */
 int qc_mactor_load(qc_mactor* a, const qc_dqn_layer layers[6]);
 /* obs [B][2][read_length] fp32 (device): the network input (MeasurementRecord.hist); the rest as
  * qc_actor_act */
@@ -502,17 +506,22 @@ int qc_learner_grads(qc_learner* l, qc_dqn_layer out[6]);
 int qc_learner_apply(qc_learner* l, const qc_dqn_layer grads[6]);
 
 /* ---------------------------------------------------------------------------------------------
- * Device learner of the measurement-input network: one TrainDQN.__call__ update (RL.py:159-232) of the inverted
- * harmonic driver's DQN_measurement (RL.py:29-78): plain Conv1d(2, 32, 13, /5) -> (32, 64, 11, /4) ->
- * (64, 64, 9, /4), ReLU each, flatten, Linear(64 T3, 256) + ReLU, fc21 / fc31 FactorizedNoisy, the mean head
+ * Device learner of the measurement-input network: one TrainDQN.__call__ update (RL.py:159-232) of
+ * DQN_measurement (RL.py:29-78), the inverted harmonic driver's or (conv_weight_norm = 1) the harmonic driver's:
+ * Conv1d(2, 32, 13, /5) -> (32, 64, 11, /4) -> (64, 64, 9, /4), ReLU each, flatten, Linear(64 T3, 256) + ReLU, fc21 / fc31 FactorizedNoisy, the mean head
  * fc22 / fc32 Linear_weight_normalize; centred LaProp, fp32 throughout on f32-input MFMA, the loss and the noise
  * as qc_learner (H2 = 256). A transition is a row of qc_record: K = read_length / read_step_length,
  *   row = [measurements (read_length + read_step_length, newest first) | forces (K + 1, newest first) | action | reward]
  * and the states are next[0] = row[0 : L], prev[0] = row[m : m + L], next[1][k m : (k + 1) m] = forces[k],
  * prev[1][k m : (k + 1) m] = forces[k + 1] (RL.py:180-192). Gradients use no atomics: the same inputs give
  * bit-identical parameters. All pointers are device pointers; every call is asynchronous on the handle's stream
- * except qc_mlearner_stats. The weight-normalised convolution stack of the harmonic driver is not implemented:
- * a conv or fc1 layer with weight_norm is refused by name. */
+ * except qc_mlearner_stats.
+ * conv_weight_norm = 0: conv1..3 are plain Conv1d layers, and a convolution with a weight_norm is refused by name.
+ * conv_weight_norm = 1: conv1..3 are Conv1d_weight_normalize layers (harmonic oscillator/RL.py:29-75,
+ * layers.py:86-94; effective weight W g / ||W||_F, one scalar g per layer): qc_mlearner_load and qc_mlearner_apply
+ * require a weight_norm on all three, qc_mlearner_layers and qc_mlearner_grads return it (25 tensors instead of
+ * 22; in the gradients the slot holds dg, as for fc22 / fc32). fc1 with a weight_norm is refused on both. The
+ * harmonic driver's handle is conv_weight_norm = 1, QC_TD_REWARD, betas (0.9, 0.999), L = 4320, m = 80. */
 typedef struct qc_mlearner qc_mlearner;
 typedef struct qc_mlearner_params {
     int32_t read_length;           /* L */
@@ -524,6 +533,7 @@ typedef struct qc_mlearner_params {
     double gamma, lr, alive_reward, failing_reward;
     double beta1, beta2;           /* LaProp's betas in [0, 1); 0: 0.9 and 0.9995 */
     uint64_t seed;                 /* Philox key of the in-kernel noise */
+    int32_t conv_weight_norm;      /* 0: plain Conv1d stack, 1: Conv1d_weight_normalize on conv1..3 */
 } qc_mlearner_params;
 int qc_mlearner_create(const qc_mlearner_params* p, int device, qc_mlearner** out);
 void qc_mlearner_destroy(qc_mlearner* l);
