@@ -53,8 +53,12 @@ __device__ __forceinline__ float noise_at(const ActArgs& a, int f, int64_t e) {
 }
 
 // W2: fc2's width (qcart_dqn.hpp). The measurement network's tail (h_in) exists at W2 = 256 only
-template <int W2>
+// W2C = W2 + kChunkTag: in_pad > kChunkIn (the 'wavefunction' input), fc1 over X0 in chunks (dense4_chunked); the rest
+// is the same
+template <int W2C>
 __global__ __launch_bounds__(kThreads) void k_actor_act(const ActArgs a) {
+    constexpr int W2 = W2C & ~kChunkTag;
+    constexpr bool CHUNK = (W2C & kChunkTag) != 0;
     constexpr int kEpsIn31 = NoiseAt<W2>::kEpsIn31, kEpsOut31 = NoiseAt<W2>::kEpsOut31,
                   kEpsIn41 = NoiseAt<W2>::kEpsIn41, kEpsOut41 = NoiseAt<W2>::kEpsOut41;
     constexpr bool kWide = W2 != kH2;
@@ -82,6 +86,13 @@ __global__ __launch_bounds__(kThreads) void k_actor_act(const ActArgs a) {
         }
         __syncthreads();
     } else {
+        if constexpr (CHUNK) {
+            // ---- input and fc1 (ReLU), X0 through RB one chunk of rows at a time
+            dense4_chunked(
+                a.L[0].u, RB, a.in_pad, tid,
+                [&](int k, int e) { return (k < a.in_len && e0 + e < a.B) ? a.obs[(e0 + e) * a.in_len + k] : 0.f; },
+                [&](int o, float y) { RA[o * kE + env] = fmaxf(y + a.L[0].ub[o], 0.f); });
+        } else {
         // ---- input: the fp32 network input (IHO/main_parallel.py:131,241) -> X0[k][env]
         for (int i = tid; i < a.in_pad * kE; i += kThreads) {
             const int k = i / kE, e = i % kE;
@@ -92,6 +103,7 @@ __global__ __launch_bounds__(kThreads) void k_actor_act(const ActArgs a) {
         dense4(a.L[0].u, nullptr, RB, nullptr, kH1, a.in_pad, lane, wave, [&](int o, float y, float) {
             RA[o * kE + env] = fmaxf(y + a.L[0].ub[o], 0.f);
         });
+        }
         __syncthreads();
         // ---- fc2: ReLU; also eps_in(fc31) o H2 for the noisy GEMM
         dense4(a.L[1].u, nullptr, RA, nullptr, W2, kH1, lane, wave, [&](int o, float y, float) {
@@ -492,6 +504,7 @@ struct ActorCore {
     bool loaded = false;
     int n_act = 0, noise_len = 0;
     int w2 = kH2;                // fc2's width (k_actor_act's instantiation); the measurement actor's tail: 256
+    bool chunked = false;        // data_length above kChunkIn: k_actor_act<w2 + kChunkTag>
     int64_t max_batch = 0;       // also the noise buffer's leading dimension
     uint64_t seed = 0;
     float* d_w = nullptr;        // all fragments + padded biases
@@ -525,9 +538,15 @@ constexpr LayerRule kMactorRules[] = {
      "fc21 / fc31: FactorizedNoisy or Linear_weight_normalize"},
 };
 
-bool enable_act_lds(int w2) {
-    const void* f = w2 == kH2Wide ? (const void*)k_actor_act<kH2Wide> : (const void*)k_actor_act<kH2>;
-    return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kActLdsBytes) == hipSuccess;
+using ActKernel = void (*)(const ActArgs);
+ActKernel act_kernel(int w2, bool chunked) {
+    if (chunked) return w2 == kH2Wide ? k_actor_act<kH2Wide + kChunkTag> : k_actor_act<kH2 + kChunkTag>;
+    return w2 == kH2Wide ? k_actor_act<kH2Wide> : k_actor_act<kH2>;
+}
+
+bool enable_act_lds(int w2, bool chunked = false) {
+    return hipFuncSetAttribute((const void*)act_kernel(w2, chunked), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)kActLdsBytes) == hipSuccess;
 }
 
 // the end of an act call: the noise (injected and transposed, or drawn), then k_actor_act; k holds the input side
@@ -559,10 +578,7 @@ int act_tail(ActorCore* a, ActArgs& k, const char* what, int64_t B, int64_t env_
     k.q_out = q_out;
     k.random_out = random_out;
     const dim3 grid((unsigned)((B + kE - 1) / kE));
-    if (a->w2 == kH2Wide)
-        hipLaunchKernelGGL(k_actor_act<kH2Wide>, grid, dim3(kThreads), kActLdsBytes, a->stream, k);
-    else
-        hipLaunchKernelGGL(k_actor_act<kH2>, grid, dim3(kThreads), kActLdsBytes, a->stream, k);
+    hipLaunchKernelGGL(act_kernel(a->w2, a->chunked), grid, dim3(kThreads), kActLdsBytes, a->stream, k);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(a->err, e, what);
     return QC_OK;
@@ -587,6 +603,7 @@ int qc_actor_create(const qc_dqn_params* p, int device, qc_actor** out) {
     a->seed = p->seed;
     a->in_pad = in_pad(p->data_length);
     a->w2 = w2;
+    a->chunked = a->in_pad > kChunkIn;
     a->noise_len = noise_len(w2, p->n_actions);
     const int K[4] = {a->in_pad, kH1, w2, kH3};
     const int O[4] = {kH1, w2, kH3, p->n_actions};
@@ -598,7 +615,7 @@ int qc_actor_create(const qc_dqn_params* p, int device, qc_actor** out) {
     hipError_t e = hipMalloc(&a->d_w, floats * sizeof(float));
     if (e == hipSuccess) e = hipMemset(a->d_w, 0, floats * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(&a->d_noise, (size_t)a->noise_len * (size_t)p->max_batch * sizeof(float));
-    const bool lds_ok = e == hipSuccess && enable_act_lds(w2);
+    const bool lds_ok = e == hipSuccess && enable_act_lds(w2, a->chunked);
     if (!lds_ok) {
         if (a->d_w) (void)hipFree(a->d_w);
         if (a->d_noise) (void)hipFree(a->d_noise);

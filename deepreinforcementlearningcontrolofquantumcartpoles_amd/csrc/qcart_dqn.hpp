@@ -22,13 +22,20 @@ constexpr int kH1 = 512, kH2 = 256, kH3 = 256, kHM = 128;   // fc1, fc2, fc31, f
 constexpr int kH2Wide = 512;
 // a params struct's hidden2 field -> the width (0: the narrow net), or 0 where it is neither
 inline int fc2_width(int hidden2) { return hidden2 == 0 || hidden2 == kH2 ? kH2 : hidden2 == kH2Wide ? kH2Wide : 0; }
-constexpr int kMaxIn = 512;      // data_length limit (LDS: [in][32] fp32 within 64 KiB)
+// X0 lives in LDS as [in_pad][32] fp32 inside one 64 KiB region: up to kChunkIn rows at once. A longer input (the
+// 'wavefunction' input: 2 (x_n - 20) floats, 1002 for the inverted quartic driver) passes through that region in
+// chunks of kChunkIn rows, fc1 accumulating over them in registers (dense4_chunked). That form of k_actor_act /
+// k_learner_fwd is the instantiation at W2 + kChunkTag (257 / 513): the tag rides on the width argument so that the
+// unchunked instantiations keep their template arguments, and with them their symbol names and their code
+constexpr int kChunkIn = 512;
+constexpr int kChunkTag = 1;
+constexpr int kMaxIn = 1024;     // data_length limit
 constexpr int kThreads = 256;    // 4 waves
 __host__ __device__ constexpr int in_pad(int data_length) { return (data_length + 1) & ~1; }
 // the create-time range checks (data_length < 0: the handle has none); null when the sizes are fine
 inline const char* bad_net_size(int data_length, int n_actions) {
-    static_assert(kMaxIn == 512, "the text below names the limit");
-    if (data_length >= 0 && (data_length < 1 || data_length > kMaxIn)) return "data_length must be in [1, 512]";
+    static_assert(kMaxIn == 1024, "the text below names the limit");
+    if (data_length >= 0 && (data_length < 1 || data_length > kMaxIn)) return "data_length must be in [1, 1024]";
     if (n_actions < 1 || n_actions > 32) return "n_actions must be in [1, 32]";
     return nullptr;
 }
@@ -82,6 +89,51 @@ __device__ __forceinline__ void dense4_hold2(const float* __restrict__ uf, const
 #pragma unroll
         for (int r = 0; r < 16; ++r) hold[j][r] = epi(t * 32 + drow(r, lane), acc[r], accs[r]);
     }
+}
+
+// One chunk of X0 into LDS: xb[k][e] = load(c0 + k, e) for k < rows, e < 32 (load answers 0 past the input's
+// end or the batch's). QCART_FC1_STAGE_K = 0: lanes along the column index e, as the unchunked kernels stage
+// (conflict-free LDS writes; every lane reads from its own input row). 1: lanes along k in runs of 8 (a wave covers
+// 8 rows x 8 columns: each run is one 32-B piece of an input row; the transposed LDS writes meet 4 to a bank), rows
+// rounded up to 8 (<= kChunkIn, inside xb)
+template <class Load>
+__device__ __forceinline__ void stage_chunk(float* xb, int c0, int rows, int tid, Load load) {
+#if QCART_FC1_STAGE_K
+    const int n = ((rows + 7) & ~7) * kE;
+    for (int i = tid; i < n; i += kThreads) {
+        const int b = i >> 6, k = (b >> 2) * 8 + (i & 7), e = (b & 3) * 8 + ((i >> 3) & 7);
+        xb[k * kE + e] = load(c0 + k, e);
+    }
+#else
+    for (int i = tid; i < rows * kE; i += kThreads) xb[i] = load(c0 + i / kE, i % kE);
+#endif
+}
+
+// fc1 for K = in_pad > kChunkIn: X0 passes through xb (LDS [kChunkIn][32]) in chunks of kChunkIn rows, staged by
+// stage_chunk between two barriers; wave w keeps its four output tiles w, w + 4, w + 8, w + 12 in registers across
+// the chunks (dense4_hold2's idea) and walks each tile's fragments [tile][k-step][64] from the chunk's first k-step.
+// epi(o, y) as dense4's, once per output after the last chunk. Every wave must call it
+template <class Load, class Epi>
+__device__ __forceinline__ void dense4_chunked(const float* __restrict__ uf, float* xb, int K, int tid, Load load,
+                                               Epi epi) {
+    static_assert(tiles(kH1) == 16, "four tiles for each of the 4 waves");
+    static_assert(kChunkIn % 2 == 0, "a chunk starts at a k-step");
+    const int lane = tid & 63, wave = tid >> 6;
+    const int S = ksteps(K);
+    f32x16 acc[4] = {};
+    for (int c0 = 0; c0 < K; c0 += kChunkIn) {
+        const int rows = K - c0 < kChunkIn ? K - c0 : kChunkIn;   // even: K is
+        if (c0) __syncthreads();   // every wave is done reading the previous chunk
+        stage_chunk(xb, c0, rows, tid, load);
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            gemm_tile(acc[j], uf + ((size_t)(wave + 4 * j) * S + c0 / 2) * 64, xb, rows / 2, lane);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) epi((wave + 4 * j) * 32 + drow(r, lane), acc[j][r]);
 }
 
 // fc41, one 32-row tile: wave 0 computes u_w H3, wave 1 sigma_w (eps_in o H3), handed over through the LDS

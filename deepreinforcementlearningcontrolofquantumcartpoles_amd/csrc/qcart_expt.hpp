@@ -58,6 +58,12 @@
 #ifndef QCART_MFC_NT
 #define QCART_MFC_NT 2
 #endif
+// DQN actor / learner, inputs above 512 floats (qcart_dqn.hpp, stage_chunk): X0's chunks staged with lanes along the
+// column index (0) or along k in runs of 8 (1; L = 1002, three alternating pairs: actor round 2.320 -> 2.312 ms,
+// learner update 0.820 -> 0.815 ms, profiles/dqn_wavefunction_ab.json)
+#ifndef QCART_FC1_STAGE_K
+#define QCART_FC1_STAGE_K 1
+#endif
 
 #ifdef QCART_STAMPS
 namespace qcart {

@@ -47,9 +47,14 @@ __device__ __forceinline__ float nz(const LArgs& a, int f, int row) { return a.n
 // HIN: the measurement network's tail (DQN_measurement, RL.py:68-74): fc1 / fc2 are skipped, relu(fc1) of
 // the convolutional stack (a.h_in, feature-major) enters as H2 at W2 = 256, and fo's fc31 / fc41 / fc32 / fc42
 // slots hold fc21 / fc31 / fc22 / fc32
-template <int W2, bool HIN = false>
+// W2C = W2 + kChunkTag: in_pad > kChunkIn (the 'wavefunction' input), fc1 over X0 in chunks (dense4_chunked); the
+// online/prev pass still writes every X0 row to the workspace, so fc1's weight gradient is k_learner_dw's as at any length
+template <int W2C, bool HIN = false>
 __global__ __launch_bounds__(kThreads) void k_learner_fwd(const LArgs a) {
+    constexpr int W2 = W2C & ~kChunkTag;
+    constexpr bool CHUNK = (W2C & kChunkTag) != 0;
     static_assert(!HIN || W2 == kH2, "the measurement network's tail exists at H2 = 256 only");
+    static_assert(!(HIN && CHUNK), "the measurement network's tail has no fc1");
     constexpr int kEpsIn31 = NoiseAt<W2>::kEpsIn31, kEpsOut31 = NoiseAt<W2>::kEpsOut31,
                   kEpsIn41 = NoiseAt<W2>::kEpsIn41, kEpsOut41 = NoiseAt<W2>::kEpsOut41;
     constexpr bool kWide = W2 != kH2;
@@ -84,6 +89,22 @@ __global__ __launch_bounds__(kThreads) void k_learner_fwd(const LArgs a) {
         }
         __syncthreads();
     } else {
+    if constexpr (CHUNK) {
+        // ---- input and fc1 (ReLU), X0 through RB one chunk of rows at a time
+        dense4_chunked(
+            F + a.fo.u[0], RB, a.in_pad, tid,
+            [&](int k, int e) {
+                if (k >= a.in_len) return 0.f;
+                const float x = a.trans[(size_t)(e0 + e) * a.row_len + (pass == 1 ? 0 : a.in_len) + k];
+                if (ws) a.X0[(size_t)k * B + e0 + e] = x;
+                return x;
+            },
+            [&](int o, float y) {
+                const float h = fmaxf(y + F[a.fo.ub[0] + o], 0.f);
+                RA[o * kE + env] = h;
+                if (ws) a.H1[(size_t)o * B + eg] = h;
+            });
+    } else {
     for (int i = tid; i < a.in_pad * kE; i += kThreads) {
         const int k = i / kE, e = i % kE;
         const float x = k < a.in_len ? a.trans[(size_t)(e0 + e) * a.row_len + (pass == 1 ? 0 : a.in_len) + k] : 0.f;
@@ -98,6 +119,7 @@ __global__ __launch_bounds__(kThreads) void k_learner_fwd(const LArgs a) {
         RA[o * kE + env] = h;
         if (ws) a.H1[(size_t)o * B + eg] = h;
     });
+    }
     __syncthreads();
 
     // ---- fc2: ReLU; eps_in(fc31) o H2
@@ -498,6 +520,7 @@ struct qc_learner {
     bool loaded = false;
     int in_pad = 0, noise_len = 0, A = 0, L = 0, B = 0;
     int w2 = kH2;             // fc2's width: the instantiation of k_learner_fwd / k_learner_bwd
+    bool chunked = false;     // data_length above kChunkIn: k_learner_fwd<w2 + kChunkTag>
     double b1 = 0, b2 = 0;    // LaProp's betas
     // host-side schedule and LaProp scalars (optimizer.py:69-80)
     int64_t updates = 0, step = 0;
@@ -526,6 +549,12 @@ struct qc_learner {
 
 namespace {
 CreateError g_learner_err;
+
+using FwdKernel = void (*)(const LArgs);
+FwdKernel fwd_kernel(int w2, bool chunked) {
+    if (chunked) return w2 == kH2Wide ? k_learner_fwd<kH2Wide + kChunkTag> : k_learner_fwd<kH2 + kChunkTag>;
+    return w2 == kH2Wide ? k_learner_fwd<kH2Wide> : k_learner_fwd<kH2>;
+}
 
 // tensor indices of layer l (fc1, fc2, fc31, fc41, fc32, fc42): weight, bias, then g | sigma_w, sigma_b
 constexpr int kFirst[6] = {0, 3, 6, 10, 14, 17};
@@ -606,6 +635,7 @@ int qc_learner_create(const qc_learner_params* p, int device, qc_learner** out) 
     const int L = l->L = p->data_length, A = l->A = p->n_actions, B = l->B = p->batch_size;
     l->in_pad = in_pad(L);
     l->w2 = w2;
+    l->chunked = l->in_pad > kChunkIn;
     l->b1 = p->beta1 != 0. ? p->beta1 : kBeta1;
     l->b2 = p->beta2 != 0. ? p->beta2 : kBeta2;
     l->noise_len = noise_len(w2, A);
@@ -751,8 +781,8 @@ int qc_learner_create(const qc_learner_params* p, int device, qc_learner** out) 
     if (e == hipSuccess) e = hipMalloc(&l->d_tiles, tl.size() * sizeof(int4));
     if (e == hipSuccess) e = hipMemcpy(l->d_tiles, tl.data(), tl.size() * sizeof(int4), hipMemcpyHostToDevice);
     if (e == hipSuccess)
-        e = hipFuncSetAttribute(w2 == kH2Wide ? (const void*)k_learner_fwd<kH2Wide> : (const void*)k_learner_fwd<kH2>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, kLdsFloats * (int)sizeof(float));
+        e = hipFuncSetAttribute((const void*)fwd_kernel(w2, l->chunked), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                kLdsFloats * (int)sizeof(float));
     if (e == hipSuccess)
         e = hipFuncSetAttribute(w2 == kH2Wide ? (const void*)k_learner_bwd<kH2Wide> : (const void*)k_learner_bwd<kH2>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, bwd_lds_floats(w2) * (int)sizeof(float));
@@ -869,10 +899,8 @@ int qc_learner_update(qc_learner* l, const float* transitions, const float* is_w
     LArgs k = l->k;
     k.trans = transitions;
     const bool wide = l->w2 == kH2Wide;
-    if (wide)
-        hipLaunchKernelGGL(k_learner_fwd<kH2Wide>, dim3(3 * B / kE), dim3(kThreads), kLdsFloats * sizeof(float), l->stream, k);
-    else
-        hipLaunchKernelGGL(k_learner_fwd<kH2>, dim3(3 * B / kE), dim3(kThreads), kLdsFloats * sizeof(float), l->stream, k);
+    hipLaunchKernelGGL(fwd_kernel(l->w2, l->chunked), dim3(3 * B / kE), dim3(kThreads), kLdsFloats * sizeof(float),
+                       l->stream, k);
     LossArgs s{};
     s.Q = k.Q; s.M = k.M; s.trans = transitions; s.w = is_weights; s.noise = l->d_noise;
     s.B = B; s.n_act = l->A; s.in_len = l->L; s.row_len = k.row_len; s.rpc = k.rpc;

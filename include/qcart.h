@@ -301,7 +301,9 @@ int qc_group_layout(qc_handle* h, int32_t* order, int64_t order_len, int32_t* mi
 typedef struct qc_actor qc_actor;
 
 typedef struct qc_dqn_params {
-    int32_t data_length;   /* network input length (5 for the 'xp' input, IHO/main_parallel.py:137-138) */
+    int32_t data_length;   /* network input length in [1, 1024]: 5 for the 'xp' input (IHO/main_parallel.py:137-138);
+                              the 'wavefunction' input's 2 (kept rows of psi): 122 (HO), 302 (QO), 322 (IHO), 1002
+                              (IQO) at the drivers' defaults. Above 512 fc1 runs over the input in chunks of 512 */
     int32_t n_actions;     /* 21 */
     int64_t max_batch;     /* largest B passed to qc_actor_act */
     uint64_t seed;         /* Philox key of the NoisyNet noise and the epsilon-greedy draws */
@@ -460,7 +462,7 @@ typedef struct qc_learner qc_learner;
  *   QC_TD_REWARD       y = gamma nsv + (1 - gamma) r             (HO; alive_reward / failing_reward unused) */
 enum { QC_TD_ALIVE = 0, QC_TD_REWARD_FAIL = 1, QC_TD_REWARD = 2 };
 typedef struct qc_learner_params {
-    int32_t data_length, n_actions;
+    int32_t data_length, n_actions; /* data_length in [1, 1024], as qc_dqn_params ('xp': 5; 'wavefunction': up to 1002) */
     int32_t batch_size;            /* multiple of 128, <= 4096 */
     int32_t backup_period;
     double gamma, lr, alive_reward, failing_reward;

@@ -8,7 +8,9 @@ Both run the same fixed batch with injected noise; per batch size: warmup update
 updates between two synchronisations (wall clock, so the host's launch cost counts, as it does in a loop).
 Prints one JSON line: ms per update at B = 128 and 512 for both paths and the learner's launches per update.
 --hidden2 512 measures the quartic drivers' net (fc2 512 -> 512; tests/dqn_variants_ref.py's restatement as baseline).
-usage: python tools/bench_learner.py [--steps K] [--warmup W] [--hidden2 {256,512}]"""
+--data-length L measures another input length (the 'wavefunction' input: 122 / 302 / 322 / 1002 floats for the HO / QO /
+IHO / IQO drivers), with tests/dqn_variants_ref.py's batches and restatement at either width.
+usage: python tools/bench_learner.py [--steps K] [--warmup W] [--hidden2 {256,512}] [--data-length L]"""
 import argparse
 import json
 import os
@@ -29,7 +31,8 @@ class TorchLearner:
     """TrainDQN.__call__ + LaProp (centered, betas (0.9, 0.9995)) as torch ops on the device."""
 
     def __init__(self, params, lr=4e-4, backup_period=300):
-        self.td_loss = R.td_loss if params["fc2.weight"].shape[0] == 256 else V.td_loss
+        narrow_xp = params["fc2.weight"].shape[0] == 256 and params["fc1.weight"].shape[1] == 5
+        self.td_loss = R.td_loss if narrow_xp else V.td_loss
         self.p = {k: v.detach().cuda().float().clone().requires_grad_(True) for k, v in params.items()}
         self.state = {k: [torch.zeros_like(v), torch.zeros_like(v), torch.zeros_like(v)] for k, v in self.p.items()}
         self.lr, self.step_count, self.l1, self.l2 = lr, 0, 0.0, 0.0
@@ -76,13 +79,17 @@ def main():
     ap.add_argument("--steps", type=int, default=300)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--hidden2", type=int, default=256, choices=(256, 512), help="fc2's width")
+    ap.add_argument("--data-length", type=int, default=5, help="the network input's length")
     args = ap.parse_args()
-    params = random_direct_dqn(seed=11, hidden2=args.hidden2)
+    L = args.data_length
+    params = random_direct_dqn(data_length=L, seed=11, hidden2=args.hidden2)
     out = {"metric": "DQN learner ms per update (direct_DQN, LaProp; device learner vs torch on the same GPU)",
-           "unit": "ms/update", "steps": args.steps, "warmup": args.warmup, "hidden2": args.hidden2}
+           "unit": "ms/update", "steps": args.steps, "warmup": args.warmup, "hidden2": args.hidden2,
+           "data_length": L}
     for B in (128, 512):
         tr, w, nz = (torch.as_tensor(a).cuda() for a in
-                      (R.make_batch(B, 2) if args.hidden2 == 256 else V.make_batch(B, 2, hidden2=args.hidden2)))
+                      (R.make_batch(B, 2) if args.hidden2 == 256 and L == 5
+                       else V.make_batch(B, 2, L=L, hidden2=args.hidden2)))
         dev = DQNLearner(params, batch_size=B)
         ref = TorchLearner(params)
         # alternate the two paths (one process, the same clock state), keep each path's best round

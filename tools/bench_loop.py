@@ -7,8 +7,12 @@ trainer's per-step memory traffic (RL.py:172, :224), with auto-reset of finished
 With --input measurements: BatchedEnv(input='measurements') (the measurement record, qc_record) +
 MeasurementActor (DQN_measurement) + the replay storing the reference's 5 915-float rows (capacity
 --capacity rows; the drivers' 2.7 M-row memory is 64 GB, the bench default keeps 262 144 rows).
+With --input wavefunction: BatchedEnv(input='wavefunction') (float32 hstack(Re, Im) of the kept rows of psi) +
+DQNActor at that length (122 / 302 / 322 / 1002 floats for --physics ho / qo / iho / iqo at the drivers' defaults;
+fc2 512 wide for the quartic drivers) + the replay storing rows of 2 L + 2 floats (capacity --capacity rows,
+default 65 536: the drivers' 12.6 M rows of 2 006 floats would be 100 GB).
 Prints one JSON line: RL steps/s (decisions), env-steps/s and the actor's / replay's share of the loop.
-usage: python tools/bench_loop.py [--batch B] [--steps K] [--input xp|measurements]"""
+usage: python tools/bench_loop.py [--batch B] [--steps K] [--input xp|wavefunction|measurements] [--physics iho|iqo|ho|qo]"""
 import argparse
 import json
 import os
@@ -32,7 +36,10 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=20)   # ~0.5 s: a fresh box ramps its clock over the first launches
     ap.add_argument("--capacity", type=int, default=0)   # xp: 7000 x 18 x 100 (IHO/arguments.py:80, main_parallel.py:595)
-    ap.add_argument("--input", choices=("xp", "measurements"), default="xp")
+    ap.add_argument("--input", choices=("xp", "wavefunction", "measurements"), default="xp")
+    ap.add_argument("--physics", choices=("iho", "iqo", "ho", "qo"), default="iho",
+                    help="with --input wavefunction: the driver whose defaults the env runs (the other inputs run "
+                         "the metric's IHO N = 512)")
     ap.add_argument("--reset", choices=("immediate", "deferred"), default=None,
                     help="BatchedEnv auto-reset mode (deferred: finished envs reset in the next call's launch, no host "
                          "sync; the default for 'xp', where it applies; immediate for 'measurements')")
@@ -46,12 +53,22 @@ def main():
         args.reset = "deferred" if args.input == "xp" else "immediate"
     B = args.batch
     meas = args.input == "measurements"
-    ph = cfg.DEFAULTS[cfg.IHO].with_(n_max=511)
+    wave = args.input == "wavefunction"
+    if args.physics != "iho" and not wave:
+        ap.error("--physics other than iho is built for --input wavefunction")
+    fam = {"iho": cfg.IHO, "iqo": cfg.IQO, "ho": cfg.HO, "qo": cfg.QO}[args.physics]
+    ph = cfg.DEFAULTS[fam] if wave else cfg.DEFAULTS[cfg.IHO].with_(n_max=511)
+    hidden2 = 512 if fam in (cfg.QO, cfg.IQO) else 256
     env = BatchedEnv(ph, B, 0, seed=1, input=args.input, reset=args.reset)
+    L = int(env.obs.shape[1]) if wave else 5
     if meas:
         actor = MeasurementActor({k: v.cuda() for k, v in random_dqn_measurement(seed=1).items()}, max_batch=B, seed=2)
         row_len = int(env.rows.shape[1])
         mem = PrioritizedReplay(args.capacity or 262144, row_len, "random", 0.2, device=0, seed=3)
+    elif wave:
+        wnet = random_direct_dqn(data_length=L, seed=1, hidden2=hidden2)
+        actor = DQNActor({k: v.cuda() for k, v in wnet.items()}, data_length=L, max_batch=B, seed=2)
+        mem = PrioritizedReplay(args.capacity or 65536, 2 * L + 2, "random", 0.2, device=0, seed=3)
     else:
         actor = DQNActor({k: v.cuda() for k, v in random_direct_dqn(seed=1).items()}, max_batch=B, seed=2)
         mem = PrioritizedReplay(args.capacity or 7000 * 18 * 100, 2 * 5 + 2, "random", 0.2, device=0, seed=3)
@@ -64,7 +81,7 @@ def main():
         assert learner.row_len == row_len
     elif args.learn:
         from deepreinforcementlearningcontrolofquantumcartpoles_amd.learner import DQNLearner
-        learner = DQNLearner(random_direct_dqn(seed=1), batch_size=512, device=0, seed=4)
+        learner = DQNLearner(wnet if wave else random_direct_dqn(seed=1), batch_size=512, device=0, seed=4)
     obs = env.reset()
     steps_done = 0
     ev = lambda: torch.cuda.Event(enable_timing=True)   # noqa: E731
@@ -117,13 +134,14 @@ def main():
     done_frac = int(n_done) / (B * args.steps)
     K = args.steps
     net = "DQN_measurement" if meas else "direct_DQN"
+    what = f"{args.physics.upper()} driver defaults" if wave else "IHO N=512"
     extra = {}
     if learner is not None:
         learn_ms = sum(a[3].elapsed_time(b[0]) for a, b in zip(marks[:-1], marks[1:]))
         extra = {"learn_steps_per_control_step": args.learn,
                  "learner_ms_per_control_step": learn_ms / max(K - 1, 1),
                  "learner_nonfinite": learner.stats()["nonfinite"]}
-    print(json.dumps({"metric": f"actor loop RL steps/s (BatchedEnv IHO N=512 input={args.input} reset={args.reset} + device {net} actor)",
+    print(json.dumps({"metric": f"actor loop RL steps/s (BatchedEnv {what} input={args.input} reset={args.reset} + device {net} actor)",
                       "value": B * K / dt, "unit": "decisions/s", "env_steps_per_s": B * K * ph.control_interval / dt,
                       # physics env-steps actually taken: the immediate mode adds the reset intervals of the envs
                       # finished in each call (deferred: they are among the B per call)
@@ -135,7 +153,7 @@ def main():
                       "replay_len": len(mem),
                       "done_fraction_per_control_step": done_frac,
                       "experience_rows_per_s": rows / dt,
-                      "row_len": mem.data_size, **extra,
+                      "row_len": mem.data_size, **({"data_length": L, "hidden2": hidden2} if wave else {}), **extra,
                       "data": f"synthetic: |0> resets, random-initialised {net} weights"}), flush=True)
 
 

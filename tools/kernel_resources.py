@@ -33,10 +33,8 @@ def code_objects(path):
         pos = data.find(MAGIC, pos + 1)
 
 
-def kernels(path):
-    """(name, vgpr_count, sgpr_count, private_segment_fixed_size, vgpr_spill_count, sgpr_spill_count) per kernel,
-    as strings. sgpr_spill_count: SGPRs the allocator spilled (into VGPR lanes: v_writelane / v_readlane on the VALU,
-    or to scratch when no lane is free)."""
+def kernel_notes(path, fields):
+    """(name, field values...) per kernel, as strings ("?" where the metadata has none)."""
     for co in code_objects(path):
         with tempfile.NamedTemporaryFile(suffix=".co") as f:
             f.write(co)
@@ -50,8 +48,21 @@ def kernels(path):
             def g(k):
                 mm = re.search(r"\." + k + r":\s+(\S+)", b)
                 return mm.group(1) if mm else "?"
-            yield (m.group(1), g("vgpr_count"), g("sgpr_count"), g("private_segment_fixed_size"), g("vgpr_spill_count"),
-                   g("sgpr_spill_count"))
+            yield (m.group(1),) + tuple(g(k) for k in fields)
+
+
+def kernels(path):
+    """(name, vgpr_count, sgpr_count, private_segment_fixed_size, vgpr_spill_count, sgpr_spill_count) per kernel,
+    as strings. sgpr_spill_count: SGPRs the allocator spilled (into VGPR lanes: v_writelane / v_readlane on the VALU,
+    or to scratch when no lane is free)."""
+    return kernel_notes(path, ("vgpr_count", "sgpr_count", "private_segment_fixed_size", "vgpr_spill_count",
+                               "sgpr_spill_count"))
+
+
+def static_lds(path):
+    """(name, group_segment_fixed_size) per kernel: the LDS bytes the kernel declares itself (`__shared__` arrays);
+    what a launch adds as dynamic LDS is the host's."""
+    return kernel_notes(path, ("group_segment_fixed_size",))
 
 
 if __name__ == "__main__":
