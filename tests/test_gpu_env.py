@@ -235,9 +235,12 @@ def test_out_of_range_actions_raise_at_the_next_check():
 
 
 def _episodes_per_env(mode, ph, B, calls, policy, reset_kind="reference"):
-    """Each env's finished episodes (return, length, first-interval flag) in its own order, and the ring."""
+    """Each env's finished episodes (return, length, first-interval flag) in its own order, and the ring.
+    env.flat: the same episodes call by call in env order; env.n_at_reset: ring entries of the initial reset."""
     env = BatchedEnv(ph, B, 0, seed=5, reset=mode, reset_kind=reset_kind)
     env.reset()
+    env.n_at_reset = sum(r.numel() for r, _ in env.finished_returns)
+    env.flat = []
     per = [[] for _ in range(B)]
     for _ in range(calls):
         obs, rew, done, info = env.step(policy(env.obs))
@@ -250,17 +253,19 @@ def _episodes_per_env(mode, ph, B, calls, policy, reset_kind="reference"):
             ret, ln = env.episode_return.cpu().numpy(), env.t.cpu().numpy()
         for e in np.nonzero(d)[0]:
             per[e].append((float(ret[e]), float(ln[e])))
+            env.flat.append((float(ret[e]), float(ln[e])))
     return per, env
 
 
-@pytest.mark.parametrize("fam, kind", [(cfg.IHO, "reference"), (cfg.IQO, "reference"), (cfg.IHO, "synthetic")])
-def test_deferred_reset_keeps_every_envs_episodes(fam, kind):
+@pytest.mark.parametrize("fam, kind, B, n_max", [(cfg.IHO, "reference", 24, 127), (cfg.IQO, "reference", 24, 0),
+                                                 (cfg.IHO, "synthetic", 24, 127), (cfg.IHO, "synthetic", 1100, 63)],
+                         ids=["1-reference", "3-reference", "1-synthetic", "1-synthetic-1100"])
+def test_deferred_reset_keeps_every_envs_episodes(fam, kind, B, n_max):
     """reset='deferred' (a finished env takes its reset interval in the next call, inside the same step launch,
     bookkeeping on the device by qc_env_tail, no host sync): every env's own episode sequence — returns and
     lengths — is bitwise the immediate mode's (per-env noise keyed by the env's own step count, a policy of the
-    observations only), just spread over more calls."""
-    ph = cfg.DEFAULTS[cfg.IHO].with_(n_max=127) if fam == cfg.IHO else cfg.DEFAULTS[cfg.IQO].with_(x_max=12.8)
-    B = 24
+    observations only), just spread over more calls. B = 1100 crosses a 1024-env chunk of qc_env_tail end to end."""
+    ph = cfg.DEFAULTS[cfg.IHO].with_(n_max=n_max) if fam == cfg.IHO else cfg.DEFAULTS[cfg.IQO].with_(x_max=12.8)
 
     def policy(obs):   # a deterministic bad controller: pushes the pole the way it leans (episodes end)
         return torch.where(obs[:, 0] > 0, 20, 0).to(torch.int32)
@@ -272,9 +277,14 @@ def test_deferred_reset_keeps_every_envs_episodes(fam, kind):
         assert imm[e][:k] == dfr[e][:k], e
         n += k
     assert n >= B   # every env finished at least one episode in both runs
-    # the ring holds the same episodes as the per-call done flags, in env order per call
+    # the ring holds the same episodes as the per-call done flags, in env order per call: the same (return,
+    # length) values, after the first-interval episodes of the initial reset (return 0, one interval long)
     fr = env.finished_returns
-    assert sum(r.numel() for r, _ in fr) == sum(len(x) for x in dfr)
+    n0 = env.n_at_reset
+    assert sum(r.numel() for r, _ in fr) - n0 == sum(len(x) for x in dfr)
+    ring_r, ring_l = torch.cat([r for r, _ in fr]).tolist(), torch.cat([t for _, t in fr]).tolist()
+    assert list(zip(ring_r, ring_l))[n0:] == env.flat
+    assert ring_r[:n0] == [0.0] * n0 and ring_l[:n0] == [ph.control_interval * ph.dt] * n0
 
 
 def test_deferred_reset_call_semantics():
@@ -302,3 +312,70 @@ def test_deferred_reset_call_semantics():
         seen += int((done & live).sum())
         prev_done = done.clone()
     assert seen >= B
+
+
+@pytest.mark.parametrize("kind", [cfg.IHO, cfg.IQO])
+def test_env_tail_matches_numpy_restatement_across_chunks_and_ring_wrap(kind):
+    """qc_env_tail called directly on synthetic step outputs, three calls chained through their outputs, bit for
+    bit against tests/env_tail_ref.py. B = 2500 is two full 1024-env chunks plus seven waves and four lanes, so
+    the per-wave offsets are nonzero and the ring base advances inside a launch; envs 1024..2047 (a whole chunk)
+    finish nothing in call 1, wave 2112..2175 finishes entirely; |<x>| sits exactly at xth (not out of bounds:
+    the test is a strict >), one ulp beyond, and far beyond. fin_cap = 1500 (at least a chunk, so two finishers
+    of one chunk never share a slot) wraps during call 2; the ring starts at fin_n = 37. kind = IQO decides by
+    term_step on the same handle."""
+    import ctypes
+    from deepreinforcementlearningcontrolofquantumcartpoles_amd import _lib as L
+    from tests.env_tail_ref import env_tail_ref
+    ph = cfg.DEFAULTS[cfg.IHO].with_(n_max=63)
+    B, n_obs, fin_cap, scaling = 2500, 5, 1500, 0.7
+    st = Stepper(ph, B, 0, seed=1)   # never stepped: the handle only carries the batch size and the stream
+    assert st.n_obs == n_obs
+    ci, dt, xth = ph.control_interval, ph.dt, ph.xth
+    rng = np.random.default_rng(17)
+    s = dict(pending=(rng.random(B) < 0.3).astype(np.uint8), t=rng.integers(1, 50, B) * (ci * dt),
+             steps=rng.integers(1, 50, B) * ci, episode_return=rng.integers(-1, 40, B).astype(np.float64),
+             fin=np.full((2, fin_cap + 1), -7.0), fin_n=37)
+    dev = {k: torch.from_numpy(np.asarray(v)).cuda() for k, v in s.items()}
+    wrapped = []
+    for call in range(3):
+        p_over = 0.1 if call != 1 else 0.7
+        fail = np.where(rng.random(B) < 0.1, rng.integers(1, ci + 1, B), 0).astype(np.int32)
+        term = np.where(rng.random(B) < p_over, rng.integers(0, ci, B), -1).astype(np.int32)
+        obs = rng.normal(size=(B, n_obs))
+        obs[:, 0] *= 5.0 if call != 1 else 20.0        # P(|x| > 8): 0.11 / 0.69
+        edge = [xth, -xth, np.nextafter(xth, np.inf), -np.nextafter(xth, np.inf), np.nextafter(xth, 0.0), 1e300,
+                -1e300, 0.0]
+        obs[5:5 + len(edge), 0] = edge
+        obs[2300:2300 + len(edge), 0] = edge
+        if call == 0:
+            fail[1024:2048], term[1024:2048] = 0, -1
+            obs[1024:2048, 0] = np.clip(obs[1024:2048, 0], -xth, xth)
+            fail[2112:2176], term[2112:2176] = 5, 3
+        want = env_tail_ref(kind, ci, dt, xth, scaling, -1.0, fail, term, obs, s["pending"], s["t"], s["steps"],
+                            s["episode_return"], s["fin"], fin_cap, s["fin_n"])
+        if call == 0:
+            assert not want["done"][1024:2048].any() and want["done"][2112:2176].all()
+        wrapped.append(want["fin_n"] // fin_cap > s["fin_n"] // fin_cap)
+        d_fail, d_term, d_obs = (torch.from_numpy(x).cuda() for x in (fail, term, obs))
+        out = dict(obs32=torch.full((B, n_obs), -3.0, dtype=torch.float32, device="cuda"),
+                   reward=torch.full((B,), -3.0, dtype=torch.float32, device="cuda"),
+                   done=torch.full((B,), 9, dtype=torch.uint8, device="cuda"),
+                   valid=torch.full((B,), 9, dtype=torch.uint8, device="cuda"))
+        a = L.QcEnvTailArgs(B=B, kind=kind, n_obs=n_obs, interval=ci, dt=dt, xth=xth, input_scaling=scaling,
+                            failing_reward=-1.0, fail_step=d_fail.data_ptr(), term_step=d_term.data_ptr(),
+                            obs=d_obs.data_ptr(), pending=dev["pending"].data_ptr(), t=dev["t"].data_ptr(),
+                            steps=dev["steps"].data_ptr(), episode_return=dev["episode_return"].data_ptr(),
+                            obs32=out["obs32"].data_ptr(), reward=out["reward"].data_ptr(),
+                            done=out["done"].data_ptr(), valid=out["valid"].data_ptr(), fin=dev["fin"].data_ptr(),
+                            fin_cap=fin_cap, fin_n=dev["fin_n"].data_ptr())
+        st._bind_stream()
+        L.check(L.lib().qc_env_tail(st._h, ctypes.byref(a)), st._h)
+        torch.cuda.synchronize()
+        for k in ("t", "steps", "episode_return", "reward", "done", "valid", "pending", "obs32", "fin"):
+            got = (out[k] if k in out else dev[k]).cpu().numpy()
+            assert got.dtype == want[k].dtype, k
+            np.testing.assert_array_equal(got, want[k], err_msg=f"call {call}: {k}")
+        assert int(dev["fin_n"]) == want["fin_n"]
+        assert (want["fin"][:, fin_cap] == -7.0).all()          # the two sink slots stay untouched
+        s = want
+    assert wrapped == [False, True, False] or wrapped == [False, True, True]   # the ring wraps during call 2

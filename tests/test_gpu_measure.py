@@ -63,6 +63,67 @@ def test_record_matches_reference_lists(family, time_steps, n_con, scaling):
             np.testing.assert_array_equal(frc[e], row_ref[L + m:L + m + K + 1])
 
 
+@pytest.mark.parametrize("time_steps,n_con,coarse_grain,read_length,vec4", [
+    (1440, 90, 1, 5760, True),     # interval 16: m = 16, K = 360: the K + 1 forces loop takes two 256-strides
+    (1440, 4, 1, 5760, True),      # interval 360: m = 360, K = 16: the m-long row tail, float4 path
+    (1611, 3, 1, 4296, False),     # interval 537: m = 537 (odd: vec4 is off although L % 4 == 0), K = 8: scalar path
+    (2148, 2, 2, 3759, False),     # interval 1074, coarse_grain 2: m = 537, L = 7 m odd as well
+])
+def test_record_past_one_stride_matches_reference_lists(time_steps, n_con, coarse_grain, read_length, vec4):
+    """qc_record's loops over K + 1 forces and over the m newest row entries stride by the 256 threads of the
+    workgroup; here K + 1 > 256 or m > 256. Synthetic q (random fp64 [interval][B], no physics stepping), a
+    frozen (mode 0) and a fresh (mode 2) env as in the test above; bit-exact against the reference lists."""
+    ph = cfg.DEFAULTS[cfg.IHO].with_(n_max=63, time_steps=time_steps, n_con=n_con)
+    B, scaling = 3, 0.7
+    st = Stepper(ph, B, 0, seed=11)
+    rec = MeasurementRecord(st, read_length=read_length, coarse_grain=coarse_grain, input_scaling=scaling)
+    L, m, K, ci = rec.read_length, rec.m, rec.K, ph.control_interval
+    assert max(K + 1, m) > 256 and ci == m * coarse_grain and L == K * m
+    # the float4 path needs L % 4 == 0 and m % 4 == 0 (and a 16-byte aligned hist, which a fresh tensor is)
+    assert vec4 == (L % 4 == 0 and m % 4 == 0) and rec.hist.data_ptr() % 16 == 0
+    orc = [MeasureLists(L, ci, coarse_grain, scaling) for _ in range(B)]
+    rows = torch.zeros((B, rec.row_len), dtype=torch.float32, device=st.device)
+    rng = np.random.default_rng(5)
+    # six control steps fill only 6 m of the history and 6 of the forces: start from a full random record
+    # (float32 values, so the lists hold them exactly) so that every stride moves nonzero data
+    h0 = rng.normal(size=(B, 2, L)).astype(np.float32)
+    f0 = rng.normal(size=(B, K + 1)).astype(np.float32)   # the last entry is the one the next step drops
+    rec.hist.copy_(torch.from_numpy(h0))
+    rec.forces.copy_(torch.from_numpy(f0))
+    for e in range(B):
+        orc[e].meas = [float(x) for x in h0[e, 0, ::-1]]
+        orc[e].frc_along = [float(x) for x in h0[e, 1, ::-1]]
+        orc[e].frc_store = [float(x) for x in f0[e, K - 1::-1]]
+        assert len(orc[e].frc_store) == K
+    for k in range(6):
+        acts = rng.integers(0, 21, B).astype(np.int32)
+        mode = np.full(B, 1, dtype=np.uint8)
+        if k == 4:
+            mode[1] = 0            # frozen: untouched, no row
+            mode[2] = 2            # a new episode for env 2
+            orc[2].reset()
+        q = rng.normal(size=(ci, B))
+        reward = rng.normal(size=B).astype(np.float32)
+        before = (rec.hist.clone(), rec.forces.clone(), rows.clone())
+        rec.record(torch.from_numpy(q).cuda(), torch.from_numpy(acts).cuda(), mode=torch.from_numpy(mode).cuda(),
+                   reward=torch.from_numpy(reward).cuda(), rows=rows)
+        hist, frc, rw = rec.hist.cpu().numpy(), rec.forces.cpu().numpy(), rows.cpu().numpy()
+        for e in range(B):
+            if mode[e] == 0:
+                assert torch.equal(rec.hist[e], before[0][e]) and torch.equal(rec.forces[e], before[1][e])
+                assert torch.equal(rows[e], before[2][e])
+                continue
+            f = ph.force(int(acts[e]))
+            for s in range(ci):
+                orc[e].physics_step(float(q[s, e]), f)
+            row_ref, net_ref = orc[e].control_step(f, int(acts[e]), float(reward[e]))
+            assert row_ref.shape == (rec.row_len,)
+            np.testing.assert_array_equal(rw[e], row_ref)
+            np.testing.assert_array_equal(hist[e], net_ref)
+            np.testing.assert_array_equal(frc[e], row_ref[L + m:L + m + K + 1])
+    st.check()
+
+
 def test_env_measurement_mode_loop():
     ph = cfg.DEFAULTS[cfg.IHO].with_(n_max=63)
     B = 16

@@ -161,3 +161,238 @@ def test_batch_update_skips_out_of_range_indices():
     n = len(tree)
     np.testing.assert_array_equal(tree[par], np.where(l < n, tree[np.minimum(l, n - 1)], 0.)
                                   + np.where(r < n, tree[np.minimum(r, n - 1)], 0.))
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Past one chunk, one wave and one row stride: k_plan's carry across 1024-row chunks and 16 waves, k_update's
+# and k_sample's second stride / block, k_copy's and k_gather's c += 256 loop (row_len 300), against the oracle
+# Memory fed row by row. Bars as in the module docstring.
+
+CAP_A, D_A, N_A = 3000, 300, 2600
+
+
+def _store_both(dev, orc, rows, valid=None):
+    dev.store(torch.from_numpy(rows).cuda(), None if valid is None else torch.from_numpy(valid).cuda())
+    for e in (range(len(rows)) if valid is None else np.nonzero(valid)[0]):
+        orc.store(rows[e])
+
+
+def _mask_a(rng):
+    """About 70 % random; rows 1024..2047 (a whole chunk) invalid; one wave of 64 all valid, one all invalid;
+    the last, partial chunk (2048..2599) mixed."""
+    valid = rng.random(N_A) < 0.7
+    valid[1024:2048] = False
+    valid[192:256] = True
+    valid[320:384] = False
+    assert valid[2048:].any() and not valid[2048:].all()
+    return valid
+
+
+def _sequential_adds(capacity, pbr):
+    """SumTree.add's sequential adds before the random regime: the float sum passes += 1 / capacity from -pbr."""
+    passes, n = -pbr, 0
+    while passes < 1.:
+        passes += 1. / capacity
+        n += 1
+    return n
+
+
+def _memory_a(check):
+    """Capacity 3000 (not a power of two), row_len 300, 'random' with passes_before_random 0.2, seed 9: an
+    unmasked store, then two masked stores of 2600 rows. The policy leaves the sequential regime after 3600
+    adds, and the mask above keeps at most 2600 - 1024 - 64 = 1512 rows per store, so two masked stores alone
+    cannot reach it: the unmasked store in front (itself more than one chunk, every row compared) is sized so
+    that the switch falls inside the second masked store at a rank beyond 1024."""
+    dev = PrioritizedReplay(CAP_A, D_A, "random", 0.2, device=0, seed=9)
+    orc = Memory(CAP_A, D_A, "random", 0.2, seed=9)
+    rng = np.random.default_rng(21)
+    masks = [_mask_a(rng), _mask_a(rng)]
+    k1, k2 = int(masks[0].sum()), int(masks[1].sum())
+    assert k2 > 1024 + 8
+    switch = 1024 + (k2 - 1024) // 2                      # rank of the first random add in the last store
+    n0 = _sequential_adds(CAP_A, 0.2) - k1 - switch
+    assert n0 > 1024
+    for call, valid in enumerate([None] + masks):
+        n = n0 if valid is None else N_A
+        rows = rng.normal(size=(n, D_A)).astype(np.float32)
+        _store_both(dev, orc, rows, valid)
+        if check:
+            _compare(dev, orc)
+            assert dev.stats()["passes"] == orc.tree.passes
+            if call < 2:
+                assert orc.rand_ctr == 0
+    assert orc.rand_ctr == k2 - switch and 0 < orc.rand_ctr < k2 - 1024   # n_seq < k, the switch past rank 1024
+    assert len(orc) == CAP_A
+    return dev, orc, rng
+
+
+def test_masked_store_across_chunks_matches_reference():
+    """1a: the compaction carry across chunks (one of them empty) and waves, a non-power-of-two tree, the
+    sequential -> random switch inside a call at a rank beyond the first chunk."""
+    _memory_a(check=True)
+
+
+@pytest.mark.parametrize("policy", ["sequential", "random"])
+def test_one_store_call_wrapping_the_memory(policy):
+    """1b: 2500 valid rows (of 2800) into capacity 700 in one call: every slot is written 3-4 times and the
+    later rank wins; with 'random' (passes_before_random 0) the 700 sequential and 1800 random ranks collide."""
+    cap, D = 700, 7
+    dev = PrioritizedReplay(cap, D, policy, 0.0, device=0, seed=5)
+    orc = Memory(cap, D, policy, 0.0, seed=5)
+    rng = np.random.default_rng(8)
+    valid = np.zeros(2800, dtype=bool)
+    valid[rng.choice(2800, 2500, replace=False)] = True
+    rows = rng.normal(size=(2800, D)).astype(np.float32)
+    _store_both(dev, orc, rows, valid)
+    _compare(dev, orc)
+    if policy == "random":
+        assert orc.rand_ctr == 1800 and dev.stats()["passes"] == orc.tree.passes
+    else:
+        assert dev.stats()["data_pointer"] == orc.tree.data_pointer == 2500 % cap
+
+
+def _sample_both(dev, orc, n, u):
+    idx, w, tr = dev.obtain_sample(n, torch.from_numpy(u).cuda())
+    b_idx, isw, out = orc.obtain_sample(n, u)
+    assert np.isfinite(isw).all()
+    np.testing.assert_array_equal(idx.cpu().numpy(), b_idx)
+    np.testing.assert_array_equal(tr.cpu().numpy(), out)
+    np.testing.assert_allclose(w.cpu().numpy(), isw, rtol=1e-6)
+    return b_idx
+
+
+def _update_both(dev, orc, b_idx, err):
+    dev.batch_update(torch.from_numpy(b_idx).cuda(), torch.from_numpy(err).cuda())
+    orc.batch_update(b_idx, err)
+    _compare(dev, orc, exact_tree=False)
+    tree, _ = dev.buffers()
+    orc.tree.tree[:] = tree.cpu().numpy()   # 1-ulp powf differences: later steps compare exactly again
+
+
+def test_wide_sample_and_update_match_reference():
+    """1c: 2048 samples (8 blocks of k_sample, rows of 300 floats through k_gather) and a 2048-entry update
+    (two strides of k_update's 1024 threads) with planted duplicates: a pair exactly 1024 apart (the same
+    thread), a pair 400 apart beyond 1024 (different threads, second stride), a triple. The errors are distinct,
+    so which duplicate wins shows in the leaf. Only the overwritten entries are clipped in this call (anything
+    clipped is 1.0 after the clip, so a clipped survivor would hide a lost maximum): the largest, at index 1100,
+    is overwritten by 1500, and Memory.max = 0.95 must still count it. A second update clips survivors too."""
+    dev, orc, rng = _memory_a(check=False)
+    n = 2048
+    b_idx = _sample_both(dev, orc, n, rng.random(n))
+    err = (rng.permutation(n) + 1).astype(np.float32) * np.float32(0.9 / n)
+    assert len(np.unique(err)) == n and err.max() <= 0.9
+    b_idx[1034] = b_idx[10]
+    b_idx[1500] = b_idx[1100]
+    b_idx[900] = b_idx[1700] = b_idx[200]
+    err[[10, 200, 900, 1100]] = [3.0, 5.0, 2.0, 7.0]
+    _update_both(dev, orc, b_idx, err)
+    assert orc.max == 0.95 and dev.stats()["max"] == pytest.approx(0.95, rel=1e-7)
+    n_nodes = dev.stats()["n_nodes"]
+    leaves = dev.buffers()[0].cpu().numpy()
+    for last in (1034, 1500, 1700):   # the later error won (no later natural duplicate of these three)
+        assert not (b_idx[last + 1:] == b_idx[last]).any()
+        assert leaves[b_idx[last]] == pytest.approx(float(np.power(err[last], np.float32(0.2))), rel=2e-7)
+    b_idx = _sample_both(dev, orc, n, rng.random(n))
+    err = np.abs(rng.normal(size=n)).astype(np.float32)
+    err[::7] *= 10
+    _update_both(dev, orc, b_idx, err)
+    _sample_both(dev, orc, n, rng.random(n))
+
+
+def test_store_xp_matches_reference_row_layout():
+    """1d: the 'xp' rows hstack((last, obs, [float32(action)], [reward])) of obs_len 149 (row_len 300: the
+    c += 256 loop crosses from obs into action / reward), 1500 rows with a mask into capacity 900 (wraps)."""
+    n, d, cap = 1500, 149, 900
+    dev = PrioritizedReplay(cap, 2 * d + 2, "sequential", device=0)
+    orc = Memory(cap, 2 * d + 2, "sequential", 0.0)
+    rng = np.random.default_rng(4)
+    last, obs = rng.normal(size=(n, d)).astype(np.float32), rng.normal(size=(n, d)).astype(np.float32)
+    act, rew = rng.integers(0, 21, n).astype(np.int32), rng.normal(size=n).astype(np.float32)
+    valid = rng.random(n) < 0.7
+    dev.store_xp(*(torch.from_numpy(x).cuda() for x in (last, obs, act, rew, valid)))
+    for e in np.nonzero(valid)[0]:
+        orc.store(np.hstack((last[e], obs[e], [np.float32(act[e])], [rew[e]])))
+    assert valid.sum() > cap
+    _compare(dev, orc)
+
+
+def test_zero_priority_leaf_is_resampled():
+    """1e: leaf 0 gets priority exactly 0 (an update with error 0 while max == 0, so epsilon is 0); the first
+    stratified draw (u = 0) descends to it and is redrawn inside its segment from the Philox tags 0x301 + t of
+    (seed, sample-call count, element)."""
+    from oracle.replay import philox_u53
+    cap, D, seed = 64, 6, 13
+    dev = PrioritizedReplay(cap, D, "sequential", device=0, seed=seed)
+    orc = Memory(cap, D, "sequential", 0.0, seed=seed)
+    rows = np.random.default_rng(2).normal(size=(cap, D)).astype(np.float32)
+    _store_both(dev, orc, rows)
+    n_nodes = dev.stats()["n_nodes"]
+    zero = np.array([n_nodes], np.int32)
+    dev.batch_update(torch.from_numpy(zero).cuda(), torch.zeros(1).cuda())
+    orc.batch_update(zero, np.zeros(1, np.float32))
+    assert orc.tree.tree[n_nodes] == 0. and orc.max == 0.
+    _compare(dev, orc)                                   # powf(0, alpha) = 0 exactly: the trees stay bit-equal
+    n, u = 4, np.array([0., .5, .5, .5])
+    idx, w, tr = (x.cpu().numpy() for x in dev.obtain_sample(n, torch.from_numpy(u).cuda()))
+    total, beta = orc.tree.total_p, orc.beta + orc.beta_increment_per_sampling
+    seg = total / n
+    assert orc.tree.get_leaf((0 + u[0]) * seg)[:2] == (n_nodes, 0.)   # the first draw is the zero leaf
+    for t in range(64):
+        leaf, p, row = orc.tree.get_leaf(seg * philox_u53(seed, 0, 0, 0x301 + t))
+        if p != 0.:
+            break
+    want = [(leaf, p, row)] + [orc.tree.get_leaf((i + u[i]) * seg) for i in range(1, n)]
+    for i, (leaf, p, row) in enumerate(want):
+        assert p != 0.
+        assert idx[i] == leaf
+        np.testing.assert_array_equal(tr[i], row)
+        isw = np.float32(np.power(p / (total / len(orc)), -beta))
+        assert np.isfinite(w[i]) and w[i] == pytest.approx(isw, rel=1e-6)
+
+
+@pytest.mark.parametrize("capacity", [3000, 5])
+def test_rebuild_repairs_a_corrupted_tree(capacity):
+    """1f: every internal node overwritten with garbage through the buffers() view; clean() restores the tree
+    bit for bit (parents are left + right in both the path updates and the rebuild)."""
+    if capacity == CAP_A:
+        dev, _, rng = _memory_a(check=False)
+    else:
+        rng = np.random.default_rng(6)
+        dev = PrioritizedReplay(capacity, 3, "random", 0.0, device=0, seed=2)
+        dev.store(torch.from_numpy(rng.normal(size=(9, 3)).astype(np.float32)).cuda())
+    ns = min(2048, capacity)
+    idx, _, _ = dev.obtain_sample(ns, torch.from_numpy(rng.random(ns)).cuda())
+    dev.batch_update(idx, torch.from_numpy(rng.random(ns).astype(np.float32)).cuda())
+    tree, _ = dev.buffers()
+    good = tree.clone()
+    n_nodes = dev.stats()["n_nodes"]
+    garbage = torch.from_numpy(rng.normal(size=n_nodes) * 1e3).cuda()
+    garbage[::3] = float("nan")
+    tree[:n_nodes] = garbage
+    assert not torch.equal(dev.buffers()[0][:n_nodes], good[:n_nodes])
+    dev.clean()
+    assert torch.equal(dev.buffers()[0], good)
+    assert bool((good[n_nodes:] > 0).all()) and float(good[0]) > 0
+
+
+@pytest.mark.parametrize("capacity", [1, 2])
+@pytest.mark.parametrize("policy", ["sequential", "random"])
+def test_capacity_one_and_two_match_reference(capacity, policy):
+    """1g: depth 0 (the leaf is the root) and depth 1: stores (one with n > capacity), samples of 1 and 2,
+    updates."""
+    D = 5
+    dev = PrioritizedReplay(capacity, D, policy, 0.0, device=0, seed=3)
+    orc = Memory(capacity, D, policy, 0.0, seed=3)
+    rng = np.random.default_rng(capacity)
+    for n, masked in [(1, False), (3, False), (4, True), (2, False)]:
+        rows = rng.normal(size=(n, D)).astype(np.float32)
+        _store_both(dev, orc, rows, np.array([True, False, True, True]) if masked else None)
+        _compare(dev, orc)
+        if policy == "random":
+            assert dev.stats()["passes"] == orc.tree.passes
+        for ns in range(1, len(orc) + 1):
+            b_idx = _sample_both(dev, orc, ns, rng.random(ns) * 0.98 + 0.01)
+            err = np.abs(rng.normal(size=ns)).astype(np.float32)
+            err[0] *= 1 + 9 * (n % 2)
+            _update_both(dev, orc, b_idx, err)
+    assert dev.stats()["beta"] == pytest.approx(orc.beta)
