@@ -99,6 +99,12 @@ class QcEnvTailArgs(ctypes.Structure):
         ("fin", ctypes.c_void_p),
         ("fin_cap", ctypes.c_int64),
         ("fin_n", ctypes.c_void_p),
+        # the cooling accounting (kind == QC_HO) and qc_record's per-env mode; zero / NULL for the cartpoles
+        ("quantity", ctypes.c_void_p),
+        ("cutoff", ctypes.c_double),
+        ("t_trunc", ctypes.c_double),
+        ("reward_multiply", ctypes.c_double),
+        ("rec_mode", ctypes.c_void_p),
     ]
 
 

@@ -982,10 +982,16 @@ int qc_env_tail(qc_handle* h, const qc_env_tail_args* in) {
     if (!h || !in) return QC_EINVAL;
     const qc_env_tail_args& x = *in;
     if (x.B != h->p.batch) return fail(h, QC_EINVAL, "env tail: B must be the handle's batch");
-    if (x.kind != QC_IHO && x.kind != QC_IQO) return fail(h, QC_EINVAL, "env tail: the cartpole families (IHO, IQO)");
+    if (x.kind == QC_QO)
+        return fail(h, QC_EINVAL, "env tail: QO's reset (a free evolution of U[15, 20] time units, redrawn until "
+                                  "accepted) is no one-interval reset");
+    if (x.kind != QC_IHO && x.kind != QC_IQO && x.kind != QC_HO) return fail(h, QC_EINVAL, "env tail: unknown kind");
     if (x.kind == QC_IQO && !x.term_step) return fail(h, QC_EINVAL, "env tail: IQO needs term_step");
-    if (x.B > 0 && (!x.fail_step || !x.obs || !x.pending || !x.t || !x.steps || !x.episode_return || !x.reward ||
-                    !x.done || !x.valid || !x.fin || !x.fin_n || x.fin_cap < 1 || x.n_obs < 1 || x.interval < 1))
+    if (x.kind == QC_HO && x.B > 0 && !x.quantity) return fail(h, QC_EINVAL, "env tail: HO needs quantity");
+    const bool need_obs = x.kind == QC_IHO || x.obs32;   // IHO decides by <x>; obs32 is converted from obs
+    if (x.B > 0 && (!x.fail_step || (need_obs && !x.obs) || !x.pending || !x.t || !x.steps || !x.episode_return ||
+                    !x.reward || !x.done || !x.valid || !x.fin || !x.fin_n || x.fin_cap < 1 || x.n_obs < 1 ||
+                    x.interval < 1))
         return fail(h, QC_EINVAL, "env tail: missing buffer or bad size");
     EnvTailArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -1011,6 +1017,11 @@ int qc_env_tail(qc_handle* h, const qc_env_tail_args* in) {
     a.fin = x.fin;
     a.fin_cap = x.fin_cap;
     a.fin_n = x.fin_n;
+    a.quantity = x.quantity;
+    a.cutoff = x.cutoff;
+    a.t_trunc = x.t_trunc;
+    a.reward_multiply = x.reward_multiply;
+    a.rec_mode = x.rec_mode;
     DeviceGuard g(h->device);
     return launch_env_tail(a, h->stream) ? fail(h, QC_EHIP, "env tail kernel launch failed") : QC_OK;
 }

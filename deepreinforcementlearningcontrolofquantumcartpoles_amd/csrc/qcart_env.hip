@@ -14,6 +14,14 @@
 //     bounds (IHO |<x>| > xth, IHO:246; IQO the outside probability passed 0.5 at some physics step,
 //     IQO:199-200); reward = failing_reward when done else 1, every transition valid, return += reward; a done
 //     env is reported (return, t) and resets in the next call.
+// kind == QC_HO: the cooling accounting (HO/main_parallel.py:222-292) on the phonon number `quantity`:
+//   * pending[e] set: as above; the episode is already over iff Fail or quantity > cutoff (no truncation check
+//     at the first control step, HO:240-246);
+//   * otherwise: t += interval dt, done = Fail or !(quantity <= cutoff) (a NaN ends the episode) or
+//     t >= t_trunc; reward = -quantity * reward_multiply; the terminal transition is not stored (valid = !done)
+//     and adds nothing to the return.
+// rec_mode[e] (optional) = 2 for an env pending on entry, else 1: qc_record's per-env mode (fresh history /
+// append) for the 'measurements' input.
 // One workgroup walks the batch in chunks of its 1024 threads, a workgroup scan per chunk placing the finished
 // episodes of the chunk after the previous ones (env order, deterministic).
 #include <hip/hip_runtime.h>
@@ -40,26 +48,50 @@ __global__ __launch_bounds__(kTailThreads) void k_env_tail(const EnvTailArgs a) 
         if (e < a.B) {
             const bool pend = a.pending[e] != 0;
             const bool fail = a.fail_step[e] > 0;
-            const bool oob = a.kind == 3 ? (a.term_step[e] >= 0) : (fabs(a.obs[(size_t)e * a.n_obs]) > a.xth);
-            const bool over = fail || oob;
             if (a.obs32)
                 for (int i = 0; i < a.n_obs; ++i)
                     a.obs32[(size_t)e * a.n_obs + i] = (float)a.obs[(size_t)e * a.n_obs + i] * (float)a.input_scaling;
+            if (a.rec_mode) a.rec_mode[e] = pend ? 2 : 1;   // qc_record: fresh history / append
+            bool over;
             double tt, ret;
             float rw;
-            if (pend) {
-                tt = ci_dt;
-                ret = 0.0;
-                rw = 0.0f;
-                a.steps[e] = a.interval;
-                a.valid[e] = 0;
+            if (a.kind == 0) {   // HO cooling
+                const double q = a.quantity[e];
+                if (pend) {
+                    tt = ci_dt;
+                    ret = 0.0;
+                    rw = 0.0f;
+                    over = fail || q > a.cutoff;   // no truncation at the first control step (HO:240-246)
+                    a.steps[e] = a.interval;
+                    a.valid[e] = 0;
+                } else {
+                    tt = __dadd_rn(a.t[e], ci_dt);
+                    over = fail || !(q <= a.cutoff) || tt >= a.t_trunc;
+                    // two rounded operations, as BatchedEnv's immediate mode does them (never one fused multiply-add)
+                    const double r = __dmul_rn(-q, a.reward_multiply);
+                    rw = (float)r;
+                    ret = __dadd_rn(a.episode_return[e], over ? 0.0 : r);
+                    a.steps[e] += a.interval;
+                    a.valid[e] = over ? 0 : 1;   // the terminal transition of a cooling episode is not stored
+                }
             } else {
-                tt = a.t[e] + ci_dt;
-                rw = over ? (float)a.failing_reward : 1.0f;
-                // the return accumulates the float64 reward values, as BatchedEnv's immediate mode does
-                ret = a.episode_return[e] + (over ? a.failing_reward : 1.0);
-                a.steps[e] += a.interval;
-                a.valid[e] = 1;
+                const bool oob =
+                    a.kind == 3 ? (a.term_step[e] >= 0) : (fabs(a.obs[(size_t)e * a.n_obs]) > a.xth);
+                over = fail || oob;
+                if (pend) {
+                    tt = ci_dt;
+                    ret = 0.0;
+                    rw = 0.0f;
+                    a.steps[e] = a.interval;
+                    a.valid[e] = 0;
+                } else {
+                    tt = a.t[e] + ci_dt;
+                    rw = over ? (float)a.failing_reward : 1.0f;
+                    // the return accumulates the float64 reward values, as BatchedEnv's immediate mode does
+                    ret = a.episode_return[e] + (over ? a.failing_reward : 1.0);
+                    a.steps[e] += a.interval;
+                    a.valid[e] = 1;
+                }
             }
             a.t[e] = tt;
             a.episode_return[e] = ret;

@@ -198,6 +198,9 @@ struct EnvTailArgs {
     double* fin;
     int64_t fin_cap;
     int64_t* fin_n;
+    const double* quantity;   // kind == QC_HO: the phonon number
+    double cutoff, t_trunc, reward_multiply;
+    uint8_t* rec_mode;        // optional
 };
 int launch_env_tail(const EnvTailArgs& a, void* stream);
 

@@ -25,7 +25,8 @@ the observation is get_data_wavefunction(state) * input_scaling: float32 hstack(
 [B][2][read_length] (measurements.MeasurementRecord, updated in place by the qc_record kernel) and the
 experience rows [B][row_len] come from the same kernel (info['rows']).
 
-Auto-reset modes (cartpoles, 'xp' input):
+Auto-reset modes (reset="deferred": HO, IHO and IQO with every input they have; QO's reset is hundreds of control
+intervals drawn from a host generator, no one-interval reset, and stays with "immediate"):
   * reset="immediate" (default): a finished env is reset and runs its zero-force first interval inside the same
     step() call, so the returned obs of a done env is already the next episode's first observation (the terminal
     one is info['terminal_obs']) — the reference actor's own interleaving; one more (partial) step launch and a few
@@ -36,7 +37,13 @@ Auto-reset modes (cartpoles, 'xp' input):
     time, the finished-episode ring) is one device kernel (qc_env_tail) and the call never synchronises with the
     host. Every env's own sequence — reset, zero-force interval, decisions on its observations, per-env noise — is
     the immediate mode's (tests/test_gpu_env.py: per-env episodes bitwise equal); only the calls they fall in
-    differ, and every call advances every env exactly one control interval.
+    differ, and every call advances every env exactly one control interval. HO: qc_phonon_number runs before the
+    tail, which applies the cooling rules (cutoff, truncation at t_max, reward -phonon * scale, the terminal
+    transition not valid). 'wavefunction': the returned and stored observation is qc_wavefunction_obs of the
+    states after the call. 'measurements': the tail also writes qc_record's per-env mode (fresh history for an
+    env in its reset interval, append otherwise); obs is the record, which holds a done env's terminal record
+    until the next call restarts it, and info['rows'] / info['valid'] are the immediate mode's
+    (tests/test_gpu_env_deferred_inputs.py: per-env rows and episodes bitwise equal).
 """
 from __future__ import annotations
 
@@ -84,8 +91,12 @@ class BatchedEnv:
         self.input = input
         if reset not in ("immediate", "deferred"):
             raise ValueError("reset must be 'immediate' or 'deferred'")
-        if reset == "deferred" and not (self.cartpole and input == "xp" and auto_reset):
-            raise ValueError("reset='deferred' is built for the cartpoles (IHO, IQO) with the 'xp' input and auto_reset")
+        if reset == "deferred" and physics.family == cfg.QO:
+            raise ValueError("reset='deferred' needs a one-interval reset: QO's is a random packet evolved freely for "
+                             "U[15, 20] time units and redrawn until accepted (QO/main_parallel.py:177-198), hundreds "
+                             "of control intervals drawn from a host generator; use reset='immediate'")
+        if reset == "deferred" and not auto_reset:
+            raise ValueError("reset='deferred' is an auto-reset mode (HO, IHO, IQO): it needs auto_reset")
         self.reset_mode = reset
         self._pending = torch.zeros(self.B, dtype=torch.uint8, device=self.dev)
         self._calls = 0
@@ -241,9 +252,14 @@ class BatchedEnv:
         reset_now = pend.clone().view(torch.bool)
         self._reset_states(reset_now)   # the immediate mode's reset (reset_kind included), masked
         acts = torch.where(reset_now, torch.full_like(actions, self.half), actions)
-        out = self.st.step(self.psi, acts, self.ci, want_fail=True, want_obs=True, want_term=(fam == cfg.IQO))
+        # the immediate mode's step call (the same outputs asked for, so the same kernels)
+        out = self.st.step(self.psi, acts, self.ci, want_fail=True, want_obs=True, want_term=(fam == cfg.IQO),
+                           want_q=self.rec is not None)
         B, n = self.B, self.st.n_obs
-        obs = torch.empty((B, n), dtype=torch.float32, device=self.dev)
+        cooling = fam == cfg.HO
+        quantity = self.st.phonon_number(self.psi) if cooling else None
+        obs = torch.empty((B, n), dtype=torch.float32, device=self.dev) if self.input == "xp" else None
+        rec_mode = torch.empty(B, dtype=torch.uint8, device=self.dev) if self.rec is not None else None
         reward = torch.empty(B, dtype=torch.float32, device=self.dev)
         done = torch.empty(B, dtype=torch.uint8, device=self.dev)
         valid = torch.empty(B, dtype=torch.uint8, device=self.dev)
@@ -253,18 +269,32 @@ class BatchedEnv:
                             fail_step=p(out["fail_step"]), term_step=p(out.get("term_step")), obs=p(out["obs"]),
                             pending=p(pend), t=p(self.t), steps=p(self.steps), episode_return=p(self.episode_return),
                             obs32=p(obs), reward=p(reward), done=p(done), valid=p(valid), fin=p(self._fin),
-                            fin_cap=self._fin_cap, fin_n=p(self._fin_n))
+                            fin_cap=self._fin_cap, fin_n=p(self._fin_n), quantity=p(quantity),
+                            cutoff=self.phonon_cutoff if cooling else 0.0,
+                            t_trunc=self.t_max - 0.01 * self.ph.dt if cooling else 0.0,
+                            reward_multiply=self.reward_multiply if cooling else 0.0, rec_mode=p(rec_mode))
         self.st._bind_stream()
         L.check(L.lib().qc_env_tail(self.st._h, ctypes.byref(a)), self.st._h)
+        valid_b = valid.view(torch.bool)
+        info = {"valid": valid_b, "reset": reset_now}
         last_obs = self.obs
+        if self.rec is not None:
+            # mode 2 (pending on entry) starts the history from empty lists (IHO:271-272), mode 1 appends; the
+            # hist of a done env holds its terminal record until the next call restarts it
+            self.rec.record(out["q"], acts, self.half, mode=rec_mode, reward=reward, rows=self.rows)
+            info["rows"] = self.rows
+            obs = self.rec.hist
+            last_obs = None   # (the record is updated in place: the rows carry both control steps)
+        elif self.input == "wavefunction":
+            obs = self.st.wavefunction_obs(self.psi, self.input_scaling)
         self.obs = obs
         self.last_action = acts
         self._calls += 1
         if self._calls % 16 == 0:   # deferred action-range errors, at most 16 calls late (synchronises)
             self.st.check()
         done_b = done.view(torch.bool)
-        info = {"valid": valid.view(torch.bool), "reset": reset_now, "t": self.t.clone(), "last_obs": last_obs,
-                "fail_step": out["fail_step"], "numerical_failure": done_b & (out["fail_step"] > 0)}
+        info.update({"t": self.t.clone(), "last_obs": last_obs, "fail_step": out["fail_step"],
+                     "numerical_failure": done_b & (out["fail_step"] > 0)})
         return obs, reward, done_b, info
 
     def step(self, actions: torch.Tensor):

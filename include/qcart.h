@@ -559,7 +559,7 @@ int qc_mlearner_apply(qc_mlearner* l, const qc_dqn_layer grads[8]);
 int qc_mlearner_states(qc_mlearner* l, const float* transitions, float* next_out, float* prev_out);
 
 /* ---- batched episode loop: the per-control-step bookkeeping of Control.do_episode --------------------------
- * (IHO/main_parallel.py:242-268, IQO/main_parallel.py:190-221; the cartpoles, 'xp' input) for every env after a
+ * (IHO/main_parallel.py:242-268, IQO/main_parallel.py:190-221; the cartpoles, described first) for every env after a
  * step call of one control interval, on the device (BatchedEnv reset="deferred"): pending[e] (in) marks the envs
  * whose call was their reset interval (the zero-th step without control): their time restarts at one interval,
  * return at 0, no valid transition; an episode over at that first control step is reported with return 0 (the
@@ -567,10 +567,19 @@ int qc_mlearner_states(qc_mlearner* l, const float* transitions, float* next_out
  * bounds (IHO |<x>| > xth: |obs[e][0]| > xth; IQO: term_step[e] >= 0), reward failing_reward / 1, valid,
  * return += reward. Done envs: (return, t) appended to the ring fin [2][fin_cap + 1] at *fin_n (env order; the
  * reference's result queue, IHO:300-327) and pending[e] (out) = 1: they reset in the next call. All device
- * pointers; obs32 [B][n_obs] = float(obs) * input_scaling (NULL: skip). No host synchronisation. */
+ * pointers; obs32 [B][n_obs] = float(obs) * input_scaling (NULL: skip). No host synchronisation.
+ * kind == QC_HO selects the cooling accounting (HO/main_parallel.py:222-292) on quantity[e], the phonon number
+ * after the step: a pending env's episode is already over iff Fail or quantity > cutoff (no truncation check at
+ * the first control step, HO:240-246). Other envs: t += interval dt, done = Fail or !(quantity <= cutoff) (a NaN
+ * quantity ends the episode here, not in the pending branch) or t >= t_trunc; reward = -quantity *
+ * reward_multiply; valid = !done (the terminal transition of a cooling episode is not stored); return += reward
+ * where valid, the product and the sum each rounded once. obs may be NULL for QC_HO when obs32 is NULL. The
+ * fields after fin_n are read for QC_HO only, except rec_mode, which every kind writes when it is not NULL; a
+ * struct that leaves them zero with kind QC_IHO or QC_IQO behaves as before they existed. QC_QO is refused: its
+ * reset (a packet evolved freely for U[15, 20] time units and redrawn until accepted) is no one-interval reset. */
 typedef struct qc_env_tail_args {
     int64_t B;
-    int32_t kind;             /* enum qc_family of the cartpole: QC_IHO or QC_IQO */
+    int32_t kind;             /* enum qc_family: QC_IHO or QC_IQO (cartpoles), QC_HO (cooling) */
     int32_t n_obs, interval;  /* observables per env; physics steps per control interval */
     int32_t pad;
     double dt, xth, input_scaling, failing_reward;
@@ -588,6 +597,11 @@ typedef struct qc_env_tail_args {
     double* fin;              /* [2][fin_cap + 1] finished (return, length) */
     int64_t fin_cap;
     int64_t* fin_n;           /* [1] episodes appended so far */
+    const double* quantity;   /* [B] QC_HO: qc_phonon_number of the states after the step; cartpoles: unused */
+    double cutoff;            /* QC_HO: the episode ends when quantity > cutoff */
+    double t_trunc;           /* QC_HO: the episode is truncated when t >= t_trunc (t_max - 0.01 dt) */
+    double reward_multiply;   /* QC_HO: reward = -quantity * reward_multiply */
+    uint8_t* rec_mode;        /* [B] or NULL: qc_record's mode, 2 for an env pending on entry, else 1 */
 } qc_env_tail_args;
 int qc_env_tail(qc_handle* h, const qc_env_tail_args* a);
 

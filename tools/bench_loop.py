@@ -42,7 +42,8 @@ def main():
                          "the metric's IHO N = 512)")
     ap.add_argument("--reset", choices=("immediate", "deferred"), default=None,
                     help="BatchedEnv auto-reset mode (deferred: finished envs reset in the next call's launch, no host "
-                         "sync; the default for 'xp', where it applies; immediate for 'measurements')")
+                         "sync; every input of --physics ho / iho / iqo, not qo; the default for 'xp', immediate for "
+                         "the other inputs)")
     ap.add_argument("--marker", action="store_true",
                     help="wrap the timed steps in a roctx range 'timed' (tools/loop_breakdown.py, rocprofv3 --marker-trace)")
     ap.add_argument("--learn", type=int, default=0,
