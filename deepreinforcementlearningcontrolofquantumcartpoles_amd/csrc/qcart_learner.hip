@@ -22,7 +22,9 @@
 // copies every backup_period updates).
 // The table-driven kernels (noise, loss, dw, wndot, opt, prep) and the <256, true> instantiations of k_learner_fwd /
 // k_learner_bwd (the measurement network's tail) also serve the measurement learner (qcart_mlearner.hip) through the
-// launchers at the end of the namespace (qcart_learner.hpp).
+// launchers behind the kernels (qcart_learner.hpp). Behind those, LearnerCore's functions: the host side of the
+// pipeline (create-time checks, tensor table, fragment and workspace layout, load, target sync, loss arguments,
+// LaProp step, stats) that qc_learner below and qc_mlearner are both written in; each handle adds its own kernels.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -38,7 +40,6 @@ namespace qcart {
 namespace learner {
 
 using namespace qcart::dqn;
-constexpr int kNT = 20;            // direct_DQN's parameter tensors
 
 __device__ __forceinline__ float nz(const LArgs& a, int f, int row) { return a.noise[f * kChunks + row / a.rpc]; }
 
@@ -506,59 +507,358 @@ void launch_mtail_bwd(hipStream_t s, const LArgs& a) {
     hipLaunchKernelGGL((k_learner_bwd<kH2, true>), dim3(a.B / kE), dim3(kThreads), bwd_lds_floats(kH2) * sizeof(float), s, a);
 }
 
+// ---- LearnerCore's functions (qcart_learner.hpp): the host side both handles are written in ----
+std::string bad_params(int max_batch, int batch_size, int backup_period, double lr, int target_mode, double beta1,
+                       double beta2) {
+    if (batch_size < 128 || batch_size > max_batch || batch_size % 128 != 0)
+        return "batch_size must be a multiple of 128 in [128, " + std::to_string(max_batch) +
+               "]: the learner implements FactorizedNoisy's 32-chunk noise branch (layers.py:57-74), not the per-row "
+               "branch of other batch sizes";
+    if (backup_period < 1) return "backup_period must be >= 1";
+    if (!(lr >= 0.)) return "lr must be >= 0";
+    if (target_mode != QC_TD_ALIVE && target_mode != QC_TD_REWARD_FAIL && target_mode != QC_TD_REWARD)
+        return "target_mode must be QC_TD_ALIVE, QC_TD_REWARD_FAIL or QC_TD_REWARD";
+    if (!(beta1 >= 0. && beta1 < 1.)) return "beta1 must be in [0, 1) (0: 0.9)";
+    if (!(beta2 >= 0. && beta2 < 1.)) return "beta2 must be in [0, 1) (0: 0.9995)";
+    return {};
+}
+
+void build_tensors(LearnerCore& c, int n, const int* O, const int* K, const bool* noisy, const bool* wnorm) {
+    int off = 0;
+    auto add = [&](int len, int kind, int wn, int w_off) {
+        c.tt.t[c.nt++] = Tensor{off, len, kind, wn, w_off};
+        off += (len + 3) & ~3;
+    };
+    c.n_layers = n;
+    for (int j = 0; j < n; ++j) {
+        c.O[j] = O[j]; c.K[j] = K[j]; c.noisy[j] = noisy[j]; c.wnorm[j] = wnorm[j];
+        c.first[j] = c.nt;
+        c.wn_of[j] = -1;
+        if (noisy[j]) {
+            add(O[j] * K[j], 0, -1, 0);
+            add(O[j], 0, -1, 0);
+            add(O[j] * K[j], 0, -1, 0);
+            add(O[j], 0, -1, 0);
+        } else if (wnorm[j]) {
+            c.wn_of[j] = c.nwn;
+            c.wn_tensors.t[c.nwn] = c.nt;
+            const int w_off = off;
+            add(O[j] * K[j], 1, c.nwn, w_off);
+            add(O[j], 0, -1, 0);
+            add(1, 2, c.nwn, w_off);
+            ++c.nwn;
+        } else {
+            add(O[j] * K[j], 0, -1, 0);
+            add(O[j], 0, -1, 0);
+        }
+    }
+    c.np = off;
+}
+
+void build_tail_frags(LearnerCore& c, const int* Kpad, int j0, int fc2) {
+    int fo = c.nf_fwd = host::frag_layout(c.n_layers, c.O, Kpad, c.noisy, c.u, c.s, c.ub, c.sb);
+    FragOff& f = c.k.fo;
+    for (int j = 0; j < 6; ++j) {
+        const int l = fc2 - 1 + j;
+        f.u[j] = c.u[l]; f.s[j] = c.s[l]; f.ub[j] = c.ub[l]; f.sb[j] = c.sb[l];
+    }
+    auto tfrag = [&](int j, int kpad) {   // fragments of W_j^T: [K_j rows][O_j pad kpad]
+        const int at = fo;
+        fo += tiles(c.K[j]) * ksteps(kpad) * 64;
+        return at;
+    };
+    const int w2 = c.K[fc2 + 1];
+    f.t2 = tfrag(fc2, w2);
+    f.t31u = tfrag(fc2 + 1, kH3);
+    f.t31s = tfrag(fc2 + 1, kH3);
+    f.t41u = tfrag(fc2 + 2, 32);
+    f.t41s = tfrag(fc2 + 2, 32);
+    f.t32 = tfrag(fc2 + 3, kHM);
+    f.w42 = fo; fo += kHM;
+    c.nf = fo;
+
+    for (int j = j0; j < c.n_layers; ++j) {
+        const Tensor* T = &c.tt.t[c.first[j]];
+        const int g_off = c.wnorm[j] ? T[2].off : -1;
+        c.prep.push_back(PrepJob{T[0].off, g_off, c.wn_of[j], c.O[j], c.K[j], 0, Kpad[j], c.u[j], T[1].off, c.ub[j]});
+        if (c.noisy[j])
+            c.prep.push_back(PrepJob{T[2].off, -1, -1, c.O[j], c.K[j], 0, Kpad[j], c.s[j], T[3].off, c.sb[j]});
+    }
+    auto tjob = [&](int j, int sigma, int kpad, int out_off) {
+        const Tensor* T = &c.tt.t[c.first[j]];
+        c.prep.push_back(PrepJob{T[sigma ? 2 : 0].off, c.wnorm[j] ? T[2].off : -1, -1, c.O[j], c.K[j], 1, kpad, out_off, -1, -1});
+    };
+    tjob(fc2, 0, w2, f.t2);
+    tjob(fc2 + 1, 0, kH3, f.t31u);
+    tjob(fc2 + 1, 1, kH3, f.t31s);
+    tjob(fc2 + 2, 0, 32, f.t41u);
+    tjob(fc2 + 2, 1, 32, f.t41s);
+    tjob(fc2 + 3, 0, kHM, f.t32);
+    const Tensor* T42 = &c.tt.t[c.first[fc2 + 4]];
+    c.prep.push_back(PrepJob{T42[0].off, T42[2].off, -1, 1, kHM, 2, kHM, f.w42, -1, -1});
+}
+
+// every feature-major array has its rows padded to 32 and its pad rows zero
+size_t tail_workspace(LearnerCore& c, int w2, int in_len, float* W) {
+    Carve take;
+    auto at = [&](size_t n) {
+        const size_t o = take(n);
+        return W ? W + o : nullptr;
+    };
+    const size_t B = (size_t)c.B;
+    LArgs& k = c.k;
+    k.Q = at(3 * B * 32); k.M = at(3 * B);
+    k.noise = c.d_noise = at((size_t)c.noise_len * kChunks);
+    if (in_len) {
+        k.X0 = at((size_t)tiles(in_len) * 32 * B);
+        k.H1 = at(kH1 * B);
+    }
+    k.H2 = at(w2 * B); k.H2e = at(w2 * B); k.A3 = at(kH3 * B); k.A3e = at(kH3 * B); k.R32 = at(kHM * B);
+    k.dQ = at(32 * B); k.dQe = at(32 * B); k.dM = at(32 * B);
+    k.dZ3 = at(kH3 * B); k.dZ3e = at(kH3 * B); k.dZ32 = at(kHM * B); k.dZ2 = at(w2 * B);
+    if (in_len) k.dZ1 = at(kH1 * B);
+    c.d_loss = at(4);
+    c.d_norm = at(kMaxWN);
+    return take.w;
+}
+
+void free_all(LearnerCore& c) {
+    for (void* q : c.allocs) (void)hipFree(q);
+    c.allocs.clear();
+}
+
+hipError_t alloc_core(LearnerCore& c, int w2, int in_len, size_t ws_floats) {
+    hipError_t e = hipSuccess;
+    for (float** q : {&c.P, &c.PT, &c.G, &c.E, &c.V, &c.MU})
+        if (e == hipSuccess) e = dalloc(c, q, (size_t)c.np);
+    if (e == hipSuccess) e = dalloc(c, &c.F, (size_t)c.nf);
+    if (e == hipSuccess) e = dalloc(c, &c.FT, (size_t)c.nf_fwd);
+    if (e == hipSuccess) e = dalloc(c, &c.ws, ws_floats);
+    if (e == hipSuccess) e = dalloc(c, &c.d_dot, 2 * kMaxWN);
+    if (e == hipSuccess) e = dalloc(c, &c.d_cnt, 2);
+    if (e == hipSuccess) e = dalloc(c, &c.d_prep, c.prep.size());
+    if (e == hipSuccess) e = hipMemcpy(c.d_prep, c.prep.data(), c.prep.size() * sizeof(PrepJob), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return e;
+    c.nprep = (int)c.prep.size();
+    tail_workspace(c, w2, in_len, c.ws);
+    c.k.F = c.F;
+    c.k.FT = c.FT;
+    c.k.n_act = c.A; c.k.B = c.B; c.k.rpc = c.B / kChunks;
+    return hipSuccess;
+}
+
+hipError_t upload_dw(LearnerCore& c, const DwJob* jobs, int n) {
+    std::vector<int4> tl;
+    for (int j = 0; j < n; ++j)
+        for (int to = 0; to < tiles(jobs[j].O); ++to)
+            for (int tk = 0; tk < tiles(jobs[j].K); ++tk) tl.push_back(int4{j, to, tk, 0});
+    c.ntiles = (int)tl.size();
+    hipError_t e = dalloc(c, &c.d_dwjobs, (size_t)n);
+    if (e == hipSuccess) e = hipMemcpy(c.d_dwjobs, jobs, n * sizeof(DwJob), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = dalloc(c, &c.d_tiles, tl.size());
+    if (e == hipSuccess) e = hipMemcpy(c.d_tiles, tl.data(), tl.size() * sizeof(int4), hipMemcpyHostToDevice);
+    return e;
+}
+
+void destroy_core(LearnerCore& c) {
+    host::Dev g(c.device);
+    (void)hipDeviceSynchronize();
+    free_all(c);
+}
+
+void layer_views(const LearnerCore& c, const float* base, qc_dqn_layer* out) {
+    for (int j = 0; j < c.n_layers; ++j) {
+        const Tensor* T = &c.tt.t[c.first[j]];
+        out[j] = qc_dqn_layer{base + T[0].off, base + T[1].off, c.wnorm[j] ? base + T[2].off : nullptr,
+                              c.noisy[j] ? base + T[2].off : nullptr, c.noisy[j] ? base + T[3].off : nullptr};
+    }
+}
+
+int set_lr(LearnerCore& c, double lr) {
+    if (!(lr >= 0.)) { c.err = "lr must be >= 0"; return QC_EINVAL; }
+    c.lr = lr;
+    return QC_OK;
+}
+
+namespace {
+// the layers' tensors -> dst (the parameters or the gradients), device to device on the stream; stops at a missing
+// tensor with hipErrorInvalidValue
+hipError_t copy_in(LearnerCore& c, float* dst, const qc_dqn_layer* layers) {
+    hipError_t e = hipSuccess;
+    auto put = [&](int ti, const float* src) {
+        const Tensor& T = c.tt.t[ti];
+        if (e == hipSuccess)
+            e = src ? hipMemcpyAsync(dst + T.off, src, (size_t)T.n * sizeof(float), hipMemcpyDeviceToDevice, c.stream)
+                    : hipErrorInvalidValue;
+    };
+    for (int j = 0; j < c.n_layers; ++j) {
+        const qc_dqn_layer& Y = layers[j];
+        put(c.first[j], Y.weight);
+        put(c.first[j] + 1, Y.bias);
+        if (c.noisy[j]) {
+            put(c.first[j] + 2, Y.sigma_w);
+            put(c.first[j] + 3, Y.sigma_b);
+        } else if (c.wnorm[j]) {
+            put(c.first[j] + 2, Y.weight_norm);
+        }
+    }
+    return e;
+}
+
+int not_loaded(LearnerCore& c) {
+    c.err = std::string(c.name) + "_load has not been called";
+    return QC_EINVAL;
+}
+}  // namespace
+
+int load_core(LearnerCore& c, const qc_dqn_layer* layers) {
+    host::Dev g(c.device);
+    hipError_t e = copy_in(c, c.P, layers);
+    const size_t pb = (size_t)c.np * sizeof(float);
+    for (float* q : {c.E, c.V, c.MU, c.G})
+        if (e == hipSuccess) e = hipMemsetAsync(q, 0, pb, c.stream);
+    if (e != hipSuccess) return host::hip_fail(c.err, e, "learner parameter copy");
+    launch_prep(c.stream, c.P, c.F, c.d_prep, c.nprep, c.d_norm);
+    e = hipGetLastError();
+    if (e != hipSuccess) return host::hip_fail(c.err, e, "learner weight preparation");
+    c.step = 0;
+    c.l1 = c.l2 = 0.;
+    c.backup_counter = 0;
+    c.loaded = true;
+    return QC_OK;
+}
+
+int begin_update(LearnerCore& c, const float* transitions, const float* is_weights, const float* unweighted_loss,
+                 const float* noise, uint64_t counter) {
+    if (!c.loaded) return not_loaded(c);
+    if (!transitions || !is_weights || !unweighted_loss) {
+        c.err = "transitions, is_weights and unweighted_loss are required";
+        return QC_EINVAL;
+    }
+    c.launches = 0;
+    // the target network follows the online one every backup_period updates (RL.py:164-169)
+    if (c.backup_counter == 0) {
+        hipError_t e = hipMemcpyAsync(c.PT, c.P, (size_t)c.np * sizeof(float), hipMemcpyDeviceToDevice, c.stream);
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(c.FT, c.F, (size_t)c.nf_fwd * sizeof(float), hipMemcpyDeviceToDevice, c.stream);
+        if (e != hipSuccess) return host::hip_fail(c.err, e, "target network copy");
+        c.launches = 2;
+    }
+    c.backup_counter = (c.backup_counter + 1) % c.backup_period;
+    launch_noise(c.stream, noise, c.d_noise, c.noise_len, c.seed, counter);
+    return QC_OK;
+}
+
+int end_update(LearnerCore& c, int n) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return host::hip_fail(c.err, e, "learner update launch");
+    c.updates += 1;
+    c.launches += n;
+    return QC_OK;
+}
+
+LossArgs loss_args(const LearnerCore& c, const float* trans, int in_len, int w2, const float* is_weights,
+                   float* unweighted_loss, float* loss) {
+    const LArgs& k = c.k;
+    LossArgs s{};
+    s.Q = k.Q; s.M = k.M; s.trans = trans; s.w = is_weights; s.noise = c.d_noise;
+    s.B = c.B; s.n_act = c.A; s.in_len = in_len; s.row_len = k.row_len; s.rpc = k.rpc;
+    s.eps_out41 = w2 + 2 * kH3;
+    s.omg = (float)(1. - c.gamma);
+    s.gamma = (float)c.gamma;
+    s.rew = (float)((1. - c.gamma) * c.alive_reward);
+    s.failing = (float)c.failing_reward;
+    s.inv_B = (float)(1. / c.B);
+    s.inv_A = (float)(1. / c.A);
+    s.dQ = k.dQ; s.dQe = k.dQe; s.dM = k.dM; s.ul = unweighted_loss; s.loss = c.d_loss; s.loss_user = loss;
+    s.cnt = c.d_cnt;
+    return s;
+}
+
+void opt_step(LearnerCore& c, int chain) {
+    c.step += 1;
+    c.l1 = c.l1 * c.b1 + (1 - c.b1) * c.lr;
+    c.l2 = c.l2 * c.b2 + (1 - c.b2);
+    OptArgs o{};
+    o.P = c.P; o.G = c.G; o.E = c.E; o.V = c.V; o.MU = c.MU;
+    o.dot = c.d_dot;
+    o.norm = c.d_norm;
+    o.chain = chain;
+    o.centered = c.step > kCenteredAfter ? 1 : 0;
+    o.beta1 = (float)c.b1;
+    o.beta2 = (float)c.b2;
+    o.omb2 = (float)(1 - c.b2);
+    o.l2 = (float)c.l2;
+    o.elr = (float)((1 - c.b1) * c.lr);
+    o.step_size = (float)(c.lr != 0. ? 1. / (c.l1 / c.lr) : 1.);
+    o.eps = (float)kEps;
+    launch_opt(c.stream, o, c.tt, c.nt);
+    launch_prep(c.stream, c.P, c.F, c.d_prep, c.nprep, c.d_norm);
+}
+
+int apply_core(LearnerCore& c, const qc_dqn_layer* grads) {
+    if (!c.loaded) return not_loaded(c);
+    host::Dev g(c.device);
+    hipError_t e = copy_in(c, c.G, grads);
+    if (e == hipErrorInvalidValue) { c.err = "every gradient tensor is required"; return QC_EINVAL; }
+    if (e != hipSuccess) return host::hip_fail(c.err, e, "learner gradient copy");
+    opt_step(c, 0);
+    e = hipGetLastError();
+    if (e != hipSuccess) return host::hip_fail(c.err, e, "learner optimizer launch");
+    return QC_OK;
+}
+
+int stats_core(LearnerCore& c, qc_learner_stats_t* out) {
+    host::Dev g(c.device);
+    int32_t cnt[2] = {0, 0};
+    hipError_t e = hipStreamSynchronize(c.stream);
+    if (e == hipSuccess) e = hipMemcpy(cnt, c.d_cnt, sizeof(cnt), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return host::hip_fail(c.err, e, "learner stats");
+    out->updates = c.updates;
+    out->step = c.step;
+    out->backup_counter = c.backup_counter;
+    out->launches_per_update = c.launches;
+    out->l1 = c.l1;
+    out->l2 = c.l2;
+    out->lr = c.lr;
+    out->nonfinite = cnt[0];
+    if (cnt[1]) {
+        // as qc_take_errors: report once, then clear the word
+        const int32_t zero = 0;
+        (void)hipMemcpy(c.d_cnt + 1, &zero, sizeof(zero), hipMemcpyHostToDevice);
+        c.err = std::string("an update since the last ") + c.name +
+                "_stats saw an action outside [0, n_actions) (clamped on the device)";
+        return QC_EINVAL;
+    }
+    return QC_OK;
+}
+
 }  // namespace learner
 }  // namespace qcart
 
 using namespace qcart::learner;
 using namespace qcart::host;
 
-struct qc_learner {
-    qc_learner_params p{};
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
-    bool loaded = false;
-    int in_pad = 0, noise_len = 0, A = 0, L = 0, B = 0;
+// the direct learner's own: which k_learner_fwd / k_learner_bwd it runs
+struct qc_learner : LearnerCore {
+    int in_pad = 0;
     int w2 = kH2;             // fc2's width: the instantiation of k_learner_fwd / k_learner_bwd
     bool chunked = false;     // data_length above kChunkIn: k_learner_fwd<w2 + kChunkTag>
-    double b1 = 0, b2 = 0;    // LaProp's betas
-    // host-side schedule and LaProp scalars (optimizer.py:69-80)
-    int64_t updates = 0, step = 0;
-    int backup_counter = 0;
-    double lr = 0, l1 = 0, l2 = 0;
-    int launches = 0;         // launches of the last update
-    TensorTable tt{};
-    int np = 0;               // floats in one parameter buffer
-    int nf = 0, nf_fwd = 0;   // floats in the fragment buffer / its forward part
-    FragOff fo{};
-    float *P = nullptr, *PT = nullptr, *G = nullptr, *E = nullptr, *V = nullptr, *MU = nullptr;
-    float *F = nullptr, *FT = nullptr;
-    float* ws = nullptr;      // workspace: Q, M, noise, activations, dY
-    size_t ws_floats = 0;
-    LArgs k{};
-    float *d_noise = nullptr, *d_loss = nullptr, *d_norm = nullptr;
-    double* d_dot = nullptr;
-    int32_t* d_cnt = nullptr;
-    DwJob* d_dwjobs = nullptr;
-    int4* d_tiles = nullptr;
-    int ntiles = 0;
-    PrepJob* d_prep = nullptr;
-    int nprep = 0;
-    WnTensors wn_tensors{};
 };
 
 namespace {
 CreateError g_learner_err;
 
-using FwdKernel = void (*)(const LArgs);
-FwdKernel fwd_kernel(int w2, bool chunked) {
+using Kernel = void (*)(const LArgs);
+Kernel fwd_kernel(int w2, bool chunked) {
     if (chunked) return w2 == kH2Wide ? k_learner_fwd<kH2Wide + kChunkTag> : k_learner_fwd<kH2 + kChunkTag>;
     return w2 == kH2Wide ? k_learner_fwd<kH2Wide> : k_learner_fwd<kH2>;
 }
+Kernel bwd_kernel(int w2) { return w2 == kH2Wide ? k_learner_bwd<kH2Wide> : k_learner_bwd<kH2>; }
 
-// tensor indices of layer l (fc1, fc2, fc31, fc41, fc32, fc42): weight, bias, then g | sigma_w, sigma_b
-constexpr int kFirst[6] = {0, 3, 6, 10, 14, 17};
+// fc1, fc2, fc31, fc41, fc32, fc42: 3 + 3 + 4 + 4 + 3 + 3 = 20 parameter tensors, four weight-normalised layers
 constexpr bool kNoisy[6] = {false, false, true, true, false, false};
+constexpr bool kWnorm[6] = {true, true, false, false, true, true};
 constexpr LayerRule kLearnerRules[] = {
     {0b001100, states_where([](bool wn, bool sw, bool sb) { return !sw || !sb || wn; }),
      "fc31 / fc41 are FactorizedNoisy layers (sigma_w and sigma_b, no weight_norm): the learner "
@@ -566,45 +866,6 @@ constexpr LayerRule kLearnerRules[] = {
     {0b110011, states_where([](bool wn, bool sw, bool sb) { return !wn || sw || sb; }),
      "fc1 / fc2 / fc32 / fc42 are Linear_weight_normalize layers (weight_norm, no sigma)"},
 };
-
-// the six layers' tensors inside one flat buffer (the parameters, the target's, or the gradients)
-void layer_views(const qc_learner* l, const float* base, qc_dqn_layer out[6]) {
-    for (int j = 0; j < 6; ++j) {
-        const Tensor* T = &l->tt.t[kFirst[j]];
-        out[j] = qc_dqn_layer{base + T[0].off, base + T[1].off, kNoisy[j] ? nullptr : base + T[2].off,
-                              kNoisy[j] ? base + T[2].off : nullptr, kNoisy[j] ? base + T[3].off : nullptr};
-    }
-}
-
-void free_all(qc_learner* l) {
-    for (void* q : {(void*)l->P, (void*)l->PT, (void*)l->G, (void*)l->E, (void*)l->V, (void*)l->MU, (void*)l->F,
-                    (void*)l->FT, (void*)l->ws, (void*)l->d_dot, (void*)l->d_cnt, (void*)l->d_dwjobs,
-                    (void*)l->d_tiles, (void*)l->d_prep})
-        if (q) (void)hipFree(q);
-}
-
-// optimizer step + fragment preparation (the tail of an update, and qc_learner_apply)
-void optimizer_and_prep(qc_learner* l, int chain) {
-    l->step += 1;
-    l->l1 = l->l1 * l->b1 + (1 - l->b1) * l->lr;
-    l->l2 = l->l2 * l->b2 + (1 - l->b2);
-    OptArgs o{};
-    o.P = l->P; o.G = l->G; o.E = l->E; o.V = l->V; o.MU = l->MU;
-    o.dot = l->d_dot;
-    o.norm = l->d_norm;
-    o.chain = chain;
-    o.centered = l->step > kCenteredAfter ? 1 : 0;
-    o.beta1 = (float)l->b1;
-    o.beta2 = (float)l->b2;
-    o.omb2 = (float)(1 - l->b2);
-    o.l2 = (float)l->l2;
-    o.elr = (float)((1 - l->b1) * l->lr);
-    o.step_size = (float)(l->lr != 0. ? 1. / (l->l1 / l->lr) : 1.);
-    o.eps = (float)kEps;
-    hipLaunchKernelGGL(k_learner_opt, dim3(64, kNT), dim3(256), 0, l->stream, o, l->tt);
-    hipLaunchKernelGGL(k_learner_prep, dim3(l->nprep, kPrepParts), dim3(1024), 0, l->stream, l->P, l->F, l->d_prep,
-                       l->d_norm);
-}
 }  // namespace
 
 extern "C" {
@@ -612,182 +873,54 @@ extern "C" {
 int qc_learner_create(const qc_learner_params* p, int device, qc_learner** out) {
     if (!out || !p) return QC_EINVAL;
     *out = nullptr;
-    auto fail = [](const char* m, int rc) { return g_learner_err.fail(m, rc); };
+    auto fail = [](const std::string& m, int rc) { return g_learner_err.fail(m, rc); };
     if (const char* m = bad_net_size(p->data_length, p->n_actions)) return fail(m, QC_EINVAL);
-    if (p->batch_size < 128 || p->batch_size > 4096 || p->batch_size % 128 != 0)
-        return fail("batch_size must be a multiple of 128 in [128, 4096]: the learner implements FactorizedNoisy's "
-                    "32-chunk noise branch (layers.py:57-74), not the per-row branch of other batch sizes",
-                    QC_EINVAL);
-    if (p->backup_period < 1) return fail("backup_period must be >= 1", QC_EINVAL);
-    if (!(p->lr >= 0.)) return fail("lr must be >= 0", QC_EINVAL);
     const int w2 = fc2_width(p->hidden2);
     if (!w2) return fail("hidden2 must be 0, 256 or 512 (fc2's width)", QC_EINVAL);
-    if (p->target_mode != QC_TD_ALIVE && p->target_mode != QC_TD_REWARD_FAIL && p->target_mode != QC_TD_REWARD)
-        return fail("target_mode must be QC_TD_ALIVE, QC_TD_REWARD_FAIL or QC_TD_REWARD", QC_EINVAL);
-    if (!(p->beta1 >= 0. && p->beta1 < 1.)) return fail("beta1 must be in [0, 1) (0: 0.9)", QC_EINVAL);
-    if (!(p->beta2 >= 0. && p->beta2 < 1.)) return fail("beta2 must be in [0, 1) (0: 0.9995)", QC_EINVAL);
+    const std::string bad =
+        bad_params(4096, p->batch_size, p->backup_period, p->lr, p->target_mode, p->beta1, p->beta2);
+    if (!bad.empty()) return fail(bad, QC_EINVAL);
     if (const int rc = check_device(device, g_learner_err, "the learner")) return rc;
 
     qc_learner* l = new qc_learner();
-    l->p = *p;
-    l->device = device;
-    l->lr = p->lr;
-    const int L = l->L = p->data_length, A = l->A = p->n_actions, B = l->B = p->batch_size;
+    const int L = p->data_length, A = p->n_actions;
+    take_params(*l, "qc_learner", *p, device, noise_len(w2, A));
     l->in_pad = in_pad(L);
     l->w2 = w2;
     l->chunked = l->in_pad > kChunkIn;
-    l->b1 = p->beta1 != 0. ? p->beta1 : kBeta1;
-    l->b2 = p->beta2 != 0. ? p->beta2 : kBeta2;
-    l->noise_len = noise_len(w2, A);
 
-    // ---- parameter tensors (offsets in multiples of 4 floats)
     const int O[6] = {kH1, w2, kH3, A, kHM, 1};
     const int K[6] = {L, kH1, w2, kH3, w2, kHM};
-    int off = 0, nwn = 0;
-    int wn_of[6] = {-1, -1, -1, -1, -1, -1};
-    auto add = [&](int ti, int n, int kind, int wn, int w_off) {
-        l->tt.t[ti] = Tensor{off, n, kind, wn, w_off};
-        off += (n + 3) & ~3;
-    };
-    for (int j = 0; j < 6; ++j) {
-        const int t0 = kFirst[j];
-        if (kNoisy[j]) {
-            add(t0, O[j] * K[j], 0, -1, 0);
-            add(t0 + 1, O[j], 0, -1, 0);
-            add(t0 + 2, O[j] * K[j], 0, -1, 0);
-            add(t0 + 3, O[j], 0, -1, 0);
-        } else {
-            wn_of[j] = nwn;
-            l->wn_tensors.t[nwn] = t0;
-            const int w_off = off;
-            add(t0, O[j] * K[j], 1, nwn, w_off);
-            add(t0 + 1, O[j], 0, -1, 0);
-            add(t0 + 2, 1, 2, nwn, w_off);
-            ++nwn;
-        }
-    }
-    l->np = off;
-
-    // ---- fragment buffer: forward fragments and padded biases, then the transposed fragments
     const int Kp[6] = {l->in_pad, kH1, w2, kH3, w2, kHM};
-    int fo = frag_layout(6, O, Kp, kNoisy, l->fo.u, l->fo.s, l->fo.ub, l->fo.sb);
-    l->nf_fwd = fo;
-    auto tfrag = [&](int j, int kpad) {   // fragments of W_j^T: [K_j rows][O_j pad kpad]
-        const int at = fo;
-        fo += tiles(K[j]) * ksteps(kpad) * 64;
-        return at;
-    };
-    l->fo.t2 = tfrag(1, w2);
-    l->fo.t31u = tfrag(2, kH3);
-    l->fo.t31s = tfrag(2, kH3);
-    l->fo.t41u = tfrag(3, 32);
-    l->fo.t41s = tfrag(3, 32);
-    l->fo.t32 = tfrag(4, kHM);
-    l->fo.w42 = fo; fo += kHM;
-    l->nf = fo;
-
-    std::vector<PrepJob> prep;
-    for (int j = 0; j < 6; ++j) {
-        const Tensor* T = &l->tt.t[kFirst[j]];
-        const int g_off = kNoisy[j] ? -1 : T[2].off;
-        prep.push_back(PrepJob{T[0].off, g_off, wn_of[j], O[j], K[j], 0, Kp[j], l->fo.u[j], T[1].off, l->fo.ub[j]});
-        if (kNoisy[j])
-            prep.push_back(PrepJob{T[2].off, -1, -1, O[j], K[j], 0, Kp[j], l->fo.s[j], T[3].off, l->fo.sb[j]});
-    }
-    auto tjob = [&](int j, int sigma, int kpad, int out_off) {
-        const Tensor* T = &l->tt.t[kFirst[j]];
-        prep.push_back(PrepJob{T[sigma ? 2 : 0].off, kNoisy[j] ? -1 : T[2].off, -1, O[j], K[j], 1, kpad, out_off, -1, -1});
-    };
-    tjob(1, 0, w2, l->fo.t2);
-    tjob(2, 0, kH3, l->fo.t31u);
-    tjob(2, 1, kH3, l->fo.t31s);
-    tjob(3, 0, 32, l->fo.t41u);
-    tjob(3, 1, 32, l->fo.t41s);
-    tjob(4, 0, kHM, l->fo.t32);
-    prep.push_back(PrepJob{l->tt.t[17].off, l->tt.t[19].off, -1, 1, kHM, 2, kHM, l->fo.w42, -1, -1});
-    l->nprep = (int)prep.size();
-
-    // ---- workspace (floats): every feature-major array has its rows padded to 32 and its pad rows zero
-    const int x0_rows = tiles(L) * 32;
-    size_t w = 0;
-    auto take = [&](size_t n) {
-        const size_t at = w;
-        w += (n + 3) & ~(size_t)3;
-        return at;
-    };
-    const size_t oQ = take((size_t)3 * B * 32), oM = take((size_t)3 * B), oN = take((size_t)l->noise_len * kChunks);
-    const size_t oX0 = take((size_t)x0_rows * B), oH1 = take((size_t)kH1 * B), oH2 = take((size_t)w2 * B),
-                 oH2e = take((size_t)w2 * B), oA3 = take((size_t)kH3 * B), oA3e = take((size_t)kH3 * B),
-                 oR32 = take((size_t)kHM * B), odQ = take((size_t)32 * B), odQe = take((size_t)32 * B),
-                 odM = take((size_t)32 * B), odZ3 = take((size_t)kH3 * B), odZ3e = take((size_t)kH3 * B),
-                 odZ32 = take((size_t)kHM * B), odZ2 = take((size_t)w2 * B), odZ1 = take((size_t)kH1 * B);
-    const size_t oLoss = take(4), oNorm = take(kMaxWN);
-    l->ws_floats = w;
+    build_tensors(*l, 6, O, K, kNoisy, kWnorm);
+    build_tail_frags(*l, Kp, 0, 1);
 
     Dev g(device);
-    const size_t pb = (size_t)l->np * sizeof(float);
-    hipError_t e = hipSuccess;
-    for (float** q : {&l->P, &l->PT, &l->G, &l->E, &l->V, &l->MU}) {
-        if (e == hipSuccess) e = hipMalloc(q, pb);
-        if (e == hipSuccess) e = hipMemset(*q, 0, pb);
-    }
-    if (e == hipSuccess) e = hipMalloc(&l->F, (size_t)l->nf * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(l->F, 0, (size_t)l->nf * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&l->FT, (size_t)l->nf_fwd * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(l->FT, 0, (size_t)l->nf_fwd * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&l->ws, w * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(l->ws, 0, w * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc(&l->d_dot, 2 * kMaxWN * sizeof(double));
-    if (e == hipSuccess) e = hipMemset(l->d_dot, 0, 2 * kMaxWN * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&l->d_cnt, 2 * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemset(l->d_cnt, 0, 2 * sizeof(int32_t));
-    if (e == hipSuccess) e = hipMalloc(&l->d_prep, prep.size() * sizeof(PrepJob));
-    if (e == hipSuccess) e = hipMemcpy(l->d_prep, prep.data(), prep.size() * sizeof(PrepJob), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        free_all(l);
+    if (alloc_core(*l, w2, L, tail_workspace(*l, w2, L, nullptr)) != hipSuccess) {
+        free_all(*l);
         delete l;
         return fail("device allocation failed", QC_ENOMEM);
     }
-    float* W = l->ws;
     LArgs& k = l->k;
-    k.F = l->F;
-    k.FT = l->FT;
-    k.fo = l->fo;
-    k.in_len = L; k.in_pad = l->in_pad; k.n_act = A; k.B = B; k.row_len = 2 * L + 2; k.rpc = B / kChunks;
-    k.noise = l->d_noise = W + oN;
-    k.Q = W + oQ; k.M = W + oM;
-    k.X0 = W + oX0; k.H1 = W + oH1; k.H2 = W + oH2; k.H2e = W + oH2e; k.A3 = W + oA3; k.A3e = W + oA3e; k.R32 = W + oR32;
-    k.dQ = W + odQ; k.dQe = W + odQe; k.dM = W + odM; k.dZ3 = W + odZ3; k.dZ3e = W + odZ3e; k.dZ32 = W + odZ32;
-    k.dZ2 = W + odZ2; k.dZ1 = W + odZ1;
-    l->d_loss = W + oLoss;
-    l->d_norm = W + oNorm;
+    k.in_len = L; k.in_pad = l->in_pad; k.row_len = 2 * L + 2;
 
-    // ---- the dW jobs and their tiles (dY, X, gradient tensor, bias gradient tensor)
-    float* G = l->G;
-    auto gt = [&](int ti) { return G + l->tt.t[ti].off; };
+    // ---- the dW jobs (dY, X, gradient tensor, bias gradient tensor)
+    auto gt = [&](int j, int i) { return l->G + l->tt.t[l->first[j] + i].off; };
     const DwJob jobs[8] = {
-        {k.dZ1, k.X0, gt(0), gt(1), kH1, L},        {k.dZ2, k.H1, gt(3), gt(4), w2, kH1},
-        {k.dZ3, k.H2, gt(6), gt(7), kH3, w2},       {k.dZ3e, k.H2e, gt(8), gt(9), kH3, w2},
-        {k.dQ, k.A3, gt(10), gt(11), A, kH3},       {k.dQe, k.A3e, gt(12), gt(13), A, kH3},
-        {k.dZ32, k.H2, gt(14), gt(15), kHM, w2},   {k.dM, k.R32, gt(17), gt(18), 1, kHM},
+        {k.dZ1, k.X0, gt(0, 0), gt(0, 1), kH1, L},       {k.dZ2, k.H1, gt(1, 0), gt(1, 1), w2, kH1},
+        {k.dZ3, k.H2, gt(2, 0), gt(2, 1), kH3, w2},      {k.dZ3e, k.H2e, gt(2, 2), gt(2, 3), kH3, w2},
+        {k.dQ, k.A3, gt(3, 0), gt(3, 1), A, kH3},        {k.dQe, k.A3e, gt(3, 2), gt(3, 3), A, kH3},
+        {k.dZ32, k.H2, gt(4, 0), gt(4, 1), kHM, w2},     {k.dM, k.R32, gt(5, 0), gt(5, 1), 1, kHM},
     };
-    std::vector<int4> tl;
-    for (int j = 0; j < 8; ++j)
-        for (int to = 0; to < tiles(jobs[j].O); ++to)
-            for (int tk = 0; tk < tiles(jobs[j].K); ++tk) tl.push_back(int4{j, to, tk, 0});
-    l->ntiles = (int)tl.size();
-    e = hipMalloc(&l->d_dwjobs, sizeof(jobs));
-    if (e == hipSuccess) e = hipMemcpy(l->d_dwjobs, jobs, sizeof(jobs), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(&l->d_tiles, tl.size() * sizeof(int4));
-    if (e == hipSuccess) e = hipMemcpy(l->d_tiles, tl.data(), tl.size() * sizeof(int4), hipMemcpyHostToDevice);
+    hipError_t e = upload_dw(*l, jobs, 8);
     if (e == hipSuccess)
         e = hipFuncSetAttribute((const void*)fwd_kernel(w2, l->chunked), hipFuncAttributeMaxDynamicSharedMemorySize,
                                 kLdsFloats * (int)sizeof(float));
     if (e == hipSuccess)
-        e = hipFuncSetAttribute(w2 == kH2Wide ? (const void*)k_learner_bwd<kH2Wide> : (const void*)k_learner_bwd<kH2>,
-                                hipFuncAttributeMaxDynamicSharedMemorySize, bwd_lds_floats(w2) * (int)sizeof(float));
+        e = hipFuncSetAttribute((const void*)bwd_kernel(w2), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                bwd_lds_floats(w2) * (int)sizeof(float));
     if (e != hipSuccess) {
-        free_all(l);
+        free_all(*l);
         delete l;
         return fail("device setup failed (job tables / LDS size of the learner kernels)", QC_EHIP);
     }
@@ -797,11 +930,7 @@ int qc_learner_create(const qc_learner_params* p, int device, qc_learner** out) 
 
 void qc_learner_destroy(qc_learner* l) {
     if (!l) return;
-    {
-        Dev g(l->device);
-        (void)hipDeviceSynchronize();
-        free_all(l);
-    }
+    destroy_core(*l);
     delete l;
 }
 
@@ -818,177 +947,43 @@ int qc_learner_noise_len(const qc_learner* l) { return l ? l->noise_len : QC_EIN
 int qc_learner_load(qc_learner* l, const qc_dqn_layer layers[6]) {
     if (!l || !layers) return QC_EINVAL;
     if (const int rc = validate_layers(layers, 6, kLearnerRules, 2, l->err)) return rc;
-    Dev g(l->device);
-    hipError_t e = hipSuccess;
-    auto put = [&](int ti, const float* src) {
-        const Tensor& T = l->tt.t[ti];
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(l->P + T.off, src, (size_t)T.n * sizeof(float), hipMemcpyDeviceToDevice, l->stream);
-    };
-    for (int j = 0; j < 6; ++j) {
-        const qc_dqn_layer& Y = layers[j];
-        put(kFirst[j], Y.weight);
-        put(kFirst[j] + 1, Y.bias);
-        if (kNoisy[j]) {
-            put(kFirst[j] + 2, Y.sigma_w);
-            put(kFirst[j] + 3, Y.sigma_b);
-        } else {
-            put(kFirst[j] + 2, Y.weight_norm);
-        }
-    }
-    const size_t pb = (size_t)l->np * sizeof(float);
-    for (float* q : {l->E, l->V, l->MU, l->G})
-        if (e == hipSuccess) e = hipMemsetAsync(q, 0, pb, l->stream);
-    if (e != hipSuccess) return hip_fail(l->err, e, "learner parameter copy");
-    hipLaunchKernelGGL(k_learner_prep, dim3(l->nprep, kPrepParts), dim3(1024), 0, l->stream, l->P, l->F, l->d_prep,
-                       l->d_norm);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(l->err, e, "learner weight preparation");
-    l->step = 0;
-    l->l1 = l->l2 = 0.;
-    l->backup_counter = 0;
-    l->loaded = true;
-    return QC_OK;
+    return load_core(*l, layers);
 }
 
 int qc_learner_layers(qc_learner* l, int target, qc_dqn_layer out[6]) {
     if (!l || !out) return QC_EINVAL;
-    layer_views(l, target ? l->PT : l->P, out);
+    layer_views(*l, target ? l->PT : l->P, out);
     return QC_OK;
 }
 
 int qc_learner_grads(qc_learner* l, qc_dqn_layer out[6]) {
     if (!l || !out) return QC_EINVAL;
-    layer_views(l, l->G, out);
+    layer_views(*l, l->G, out);
     return QC_OK;
 }
 
-int qc_learner_set_lr(qc_learner* l, double lr) {
-    if (!l) return QC_EINVAL;
-    if (!(lr >= 0.)) { l->err = "lr must be >= 0"; return QC_EINVAL; }
-    l->lr = lr;
-    return QC_OK;
-}
+int qc_learner_set_lr(qc_learner* l, double lr) { return l ? set_lr(*l, lr) : QC_EINVAL; }
 
 int qc_learner_update(qc_learner* l, const float* transitions, const float* is_weights, const float* noise,
                       uint64_t counter, float* unweighted_loss, float* loss) {
     if (!l) return QC_EINVAL;
-    if (!l->loaded) { l->err = "qc_learner_load has not been called"; return QC_EINVAL; }
-    if (!transitions || !is_weights || !unweighted_loss) {
-        l->err = "transitions, is_weights and unweighted_loss are required";
-        return QC_EINVAL;
-    }
     Dev g(l->device);
-    int launches = 0;
-    // the target network follows the online one every backup_period updates (RL.py:164-169)
-    if (l->backup_counter == 0) {
-        hipError_t e = hipMemcpyAsync(l->PT, l->P, (size_t)l->np * sizeof(float), hipMemcpyDeviceToDevice, l->stream);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(l->FT, l->F, (size_t)l->nf_fwd * sizeof(float), hipMemcpyDeviceToDevice, l->stream);
-        if (e != hipSuccess) return hip_fail(l->err, e, "target network copy");
-        launches += 2;
-    }
-    l->backup_counter = (l->backup_counter + 1) % l->p.backup_period;
-
+    if (const int rc = begin_update(*l, transitions, is_weights, unweighted_loss, noise, counter)) return rc;
     const int B = l->B;
-    {
-        const int n = noise ? kChunks * l->noise_len : kChunks * ((l->noise_len + 1) / 2);
-        hipLaunchKernelGGL(k_learner_noise, dim3((n + 255) / 256), dim3(256), 0, l->stream, noise, l->d_noise,
-                           l->noise_len, l->p.seed, counter);
-    }
+    hipStream_t s = l->stream;
     LArgs k = l->k;
     k.trans = transitions;
-    const bool wide = l->w2 == kH2Wide;
-    hipLaunchKernelGGL(fwd_kernel(l->w2, l->chunked), dim3(3 * B / kE), dim3(kThreads), kLdsFloats * sizeof(float),
-                       l->stream, k);
-    LossArgs s{};
-    s.Q = k.Q; s.M = k.M; s.trans = transitions; s.w = is_weights; s.noise = l->d_noise;
-    s.B = B; s.n_act = l->A; s.in_len = l->L; s.row_len = k.row_len; s.rpc = k.rpc;
-    s.eps_out41 = l->w2 + 2 * kH3;
-    s.omg = (float)(1. - l->p.gamma);
-    s.gamma = (float)l->p.gamma;
-    s.rew = (float)((1. - l->p.gamma) * l->p.alive_reward);
-    s.failing = (float)l->p.failing_reward;
-    s.inv_B = (float)(1. / B);
-    s.inv_A = (float)(1. / l->A);
-    s.dQ = k.dQ; s.dQe = k.dQe; s.dM = k.dM; s.ul = unweighted_loss; s.loss = l->d_loss; s.loss_user = loss;
-    s.cnt = l->d_cnt;
-    if (l->p.target_mode == QC_TD_REWARD_FAIL)
-        hipLaunchKernelGGL(k_learner_loss<QC_TD_REWARD_FAIL>, dim3(1), dim3(1024), 0, l->stream, s);
-    else if (l->p.target_mode == QC_TD_REWARD)
-        hipLaunchKernelGGL(k_learner_loss<QC_TD_REWARD>, dim3(1), dim3(1024), 0, l->stream, s);
-    else
-        hipLaunchKernelGGL(k_learner_loss<QC_TD_ALIVE>, dim3(1), dim3(1024), 0, l->stream, s);
-    if (wide)
-        hipLaunchKernelGGL(k_learner_bwd<kH2Wide>, dim3(B / kE), dim3(kThreads), bwd_lds_floats(kH2Wide) * sizeof(float),
-                           l->stream, k);
-    else
-        hipLaunchKernelGGL(k_learner_bwd<kH2>, dim3(B / kE), dim3(kThreads), bwd_lds_floats(kH2) * sizeof(float), l->stream, k);
-    hipLaunchKernelGGL(k_learner_dw, dim3((l->ntiles + 3) / 4), dim3(kThreads), 0, l->stream, l->d_dwjobs, l->d_tiles,
-                       l->ntiles, B);
-    hipLaunchKernelGGL(k_learner_wndot, dim3(4), dim3(1024), 0, l->stream, l->P, l->G, l->wn_tensors, l->tt, l->d_dot);
-    optimizer_and_prep(l, 1);
-    launches += 8;
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(l->err, e, "learner update launch");
-    l->updates += 1;
-    l->launches = launches;
-    return QC_OK;
+    hipLaunchKernelGGL(fwd_kernel(l->w2, l->chunked), dim3(3 * B / kE), dim3(kThreads), kLdsFloats * sizeof(float), s, k);
+    launch_loss(s, l->target_mode, loss_args(*l, transitions, k.in_len, l->w2, is_weights, unweighted_loss, loss));
+    hipLaunchKernelGGL(bwd_kernel(l->w2), dim3(B / kE), dim3(kThreads), bwd_lds_floats(l->w2) * sizeof(float), s, k);
+    launch_dw(s, l->d_dwjobs, l->d_tiles, l->ntiles, B);
+    launch_wndot(s, l->nwn, l->P, l->G, l->wn_tensors, l->tt, l->d_dot);
+    opt_step(*l, 1);
+    return end_update(*l, 8);
 }
 
-int qc_learner_apply(qc_learner* l, const qc_dqn_layer grads[6]) {
-    if (!l || !grads) return QC_EINVAL;
-    if (!l->loaded) { l->err = "qc_learner_load has not been called"; return QC_EINVAL; }
-    Dev g(l->device);
-    hipError_t e = hipSuccess;
-    auto put = [&](int ti, const float* src) {
-        const Tensor& T = l->tt.t[ti];
-        if (!src) { l->err = "every gradient tensor is required"; e = hipErrorInvalidValue; return; }
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(l->G + T.off, src, (size_t)T.n * sizeof(float), hipMemcpyDeviceToDevice, l->stream);
-    };
-    for (int j = 0; j < 6 && e == hipSuccess; ++j) {
-        const qc_dqn_layer& Y = grads[j];
-        put(kFirst[j], Y.weight);
-        put(kFirst[j] + 1, Y.bias);
-        if (kNoisy[j]) {
-            put(kFirst[j] + 2, Y.sigma_w);
-            put(kFirst[j] + 3, Y.sigma_b);
-        } else {
-            put(kFirst[j] + 2, Y.weight_norm);
-        }
-    }
-    if (e == hipErrorInvalidValue) return QC_EINVAL;
-    if (e != hipSuccess) return hip_fail(l->err, e, "learner gradient copy");
-    optimizer_and_prep(l, 0);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(l->err, e, "learner optimizer launch");
-    return QC_OK;
-}
+int qc_learner_apply(qc_learner* l, const qc_dqn_layer grads[6]) { return l && grads ? apply_core(*l, grads) : QC_EINVAL; }
 
-int qc_learner_stats(qc_learner* l, qc_learner_stats_t* out) {
-    if (!l || !out) return QC_EINVAL;
-    Dev g(l->device);
-    int32_t cnt[2] = {0, 0};
-    hipError_t e = hipStreamSynchronize(l->stream);
-    if (e == hipSuccess) e = hipMemcpy(cnt, l->d_cnt, sizeof(cnt), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail(l->err, e, "learner stats");
-    out->updates = l->updates;
-    out->step = l->step;
-    out->backup_counter = l->backup_counter;
-    out->launches_per_update = l->launches;
-    out->l1 = l->l1;
-    out->l2 = l->l2;
-    out->lr = l->lr;
-    out->nonfinite = cnt[0];
-    if (cnt[1]) {
-        // as qc_take_errors: report once, then clear the word
-        const int32_t zero = 0;
-        (void)hipMemcpy(l->d_cnt + 1, &zero, sizeof(zero), hipMemcpyHostToDevice);
-        l->err = "an update since the last qc_learner_stats saw an action outside [0, n_actions) (clamped on the device)";
-        return QC_EINVAL;
-    }
-    return QC_OK;
-}
+int qc_learner_stats(qc_learner* l, qc_learner_stats_t* out) { return l && out ? stats_core(*l, out) : QC_EINVAL; }
 
 }  // extern "C"

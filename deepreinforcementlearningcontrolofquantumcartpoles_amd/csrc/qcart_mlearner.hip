@@ -9,7 +9,10 @@
 // dense weight gradients, the optimizer and the dense fragment preparation are the direct learner's kernels
 // (qcart_learner.hip) driven through qcart_learner.hpp. New here: the state assembly, the backward of fc1 and
 // of the convolutions (all GEMMs on v_mfma_f32_32x32x2_f32, exact fp32), the split-K reduction and the
-// convolutions' fragment preparation.
+// convolutions' fragment preparation. The host side is LearnerCore's (qcart_learner.hpp: checks, tensor table,
+// the tail's fragments and workspace, load, target sync, loss arguments, LaProp step, stats); qc_mlearner adds
+// the geometry, the convolutional stack's buffers and job tables, and launches k_mlearner_prep itself behind
+// every shared fragment preparation.
 //
 // Launches per update (plain launches on the handle's stream; no atomic touches a gradient):
 //    1 k_learner_noise     the 32 chunks' noise
@@ -297,8 +300,8 @@ using namespace qcart::host;
 
 namespace {
 // parameter tensors: 6 conv, 2 fc1, 4 + 4 noisy, 3 + 3 weight-normalised = 22; a weight-normalised convolution
-// stack adds one g per convolution: 25 (qc_mlearner::nt). The layers are conv1, conv2, conv3, fc1, fc21, fc31,
-// fc22, fc32; a layer's tensors are weight, bias, then g | sigma_w, sigma_b (qc_mlearner::first: its first tensor)
+// stack adds one g per convolution: 25 (LearnerCore::nt). The layers are conv1, conv2, conv3, fc1, fc21, fc31,
+// fc22, fc32
 constexpr int kC[3] = {32, 64, 64}, kCI[3] = {2, 32, 64}, kKS[3] = {13, 11, 9}, kS[3] = {5, 4, 4};
 constexpr bool kNoisy[8] = {false, false, false, false, true, true, false, false};
 constexpr bool kWnormTail[8] = {false, false, false, false, false, false, true, true};
@@ -306,103 +309,32 @@ const char* const kName[8] = {"conv1", "conv2", "conv3", "fc1", "fc21", "fc31", 
 int conv_out(int n, int k, int s) { return (n - (k - 1) + (s - 1)) / s; }   // calculate_next_layer_dim (RL.py:49-50)
 }  // namespace
 
-struct qc_mlearner {
-    qc_mlearner_params p{};
-    int device = 0;
-    hipStream_t stream = nullptr;
-    std::string err;
-    bool loaded = false;
-    int L = 0, m = 0, K = 0, row_len = 0, A = 0, B = 0, noise_len = 0;
+// the measurement learner's own: the geometry, the convolutional stack's activations, gradients and job tables
+struct qc_mlearner : LearnerCore {
+    int L = 0, m = 0, Kf = 0, row_len = 0;   // Kf = L / m forces per state
     int T[4] = {0, 0, 0, 0};     // L, T1, T2, T3
     int Tp[4] = {0, 0, 0, 0};    // padded row length of dY1, dY2, dY3 (index 1..3)
     int flat = 0;
-    double b1 = 0, b2 = 0;
-    int64_t updates = 0, step = 0;
-    int backup_counter = 0;
-    double lr = 0, l1 = 0, l2 = 0;
-    int launches = 0;
     bool cwn = false;            // weight-normalised convolutions (qc_mlearner_params::conv_weight_norm)
-    bool wnorm[8]{};             // layer l carries a weight_norm: fc22, fc32, and conv1..3 if cwn
-    int first[8]{}, nt = 0, nwn = 0;   // layer l's first tensor; tensors; weight-normalised layers
-    TensorTable tt{};
-    int np = 0, nf = 0, nf_fwd = 0;
     int weff[3] = {0, 0, 0};     // cwn: the convolutions' effective weights [CO][CI KS], behind the fragments in F
-    int u8[8]{}, s8[8]{}, ub8[8]{}, sb8[8]{};   // forward fragments / padded biases of the 8 layers
-    int tfc1 = 0, tconv[3] = {0, 0, 0};         // fc1^T; conv2^T, conv3^T per-phase fragments (index 1, 2)
-    float *P = nullptr, *PT = nullptr, *G = nullptr, *E = nullptr, *V = nullptr, *MU = nullptr;
-    float *F = nullptr, *FT = nullptr, *ws = nullptr;
+    int tconv[3] = {0, 0, 0};    // conv2^T, conv3^T per-phase fragments (index 1, 2); fc1^T is k.fo.t2
     float *X = nullptr, *y[4] = {nullptr, nullptr, nullptr, nullptr};   // y[1..3]: [3B] env-major activations
     float *y3f = nullptr, *h1 = nullptr, *y3p = nullptr;                // [flat][3B], [256][3B], [flat][B]
     float* dY[4] = {nullptr, nullptr, nullptr, nullptr};                // padded [B][C][Tp], index 1..3
     float *part[3] = {nullptr, nullptr, nullptr}, *partb[3] = {nullptr, nullptr, nullptr};
     int epc[3] = {2, 2, 8}, tl[3] = {128, 0, 0}, nseg[3] = {1, 1, 1}, nchunks[3] = {0, 0, 0};
-    LArgs k{};
-    float *d_noise = nullptr, *d_loss = nullptr, *d_norm = nullptr;
-    double* d_dot = nullptr;
-    int32_t* d_cnt = nullptr;
-    DwJob* d_dwjobs = nullptr;
-    int4* d_tiles = nullptr;
-    int ntiles = 0;
-    PrepJob* d_prep = nullptr;
-    int nprep = 0;
     ConvPrepJobs cprep{};
     int cprep_blocks = 0;
     RedJobs red{};
-    WnTensors wn_tensors{};
-    std::vector<void*> allocs;
 };
 
 namespace {
 CreateError g_mlearner_err;
 
-void layer_views(const qc_mlearner* l, const float* base, qc_dqn_layer out[8]) {
-    for (int j = 0; j < 8; ++j) {
-        const Tensor* T = &l->tt.t[l->first[j]];
-        out[j] = qc_dqn_layer{base + T[0].off, base + T[1].off, l->wnorm[j] ? base + T[2].off : nullptr,
-                              kNoisy[j] ? base + T[2].off : nullptr, kNoisy[j] ? base + T[3].off : nullptr};
-    }
-}
-
-void free_all(qc_mlearner* l) {
-    for (void* q : l->allocs)
-        if (q) (void)hipFree(q);
-    l->allocs.clear();
-}
-
-template <class T>
-hipError_t dalloc(qc_mlearner* l, T** q, size_t n) {
-    hipError_t e = hipMalloc(q, n * sizeof(T));
-    if (e != hipSuccess) return e;
-    l->allocs.push_back(*q);
-    return hipMemset(*q, 0, n * sizeof(T));
-}
-
+// behind every k_learner_prep (load, and the LaProp step of update and apply): the convolutions' fragments
 void launch_conv_prep(qc_mlearner* l) {
     hipLaunchKernelGGL(k_mlearner_prep, dim3(l->cprep_blocks, 5), dim3(256), 0, l->stream, l->P,
                        l->cwn ? l->F : l->P, l->F, l->cprep);
-}
-
-// optimizer step + fragment preparation (the tail of an update, and qc_mlearner_apply): 3 launches
-void optimizer_and_prep(qc_mlearner* l, int chain) {
-    l->step += 1;
-    l->l1 = l->l1 * l->b1 + (1 - l->b1) * l->lr;
-    l->l2 = l->l2 * l->b2 + (1 - l->b2);
-    OptArgs o{};
-    o.P = l->P; o.G = l->G; o.E = l->E; o.V = l->V; o.MU = l->MU;
-    o.dot = l->d_dot;
-    o.norm = l->d_norm;
-    o.chain = chain;
-    o.centered = l->step > kCenteredAfter ? 1 : 0;
-    o.beta1 = (float)l->b1;
-    o.beta2 = (float)l->b2;
-    o.omb2 = (float)(1 - l->b2);
-    o.l2 = (float)l->l2;
-    o.elr = (float)((1 - l->b1) * l->lr);
-    o.step_size = (float)(l->lr != 0. ? 1. / (l->l1 / l->lr) : 1.);
-    o.eps = (float)kEps;
-    launch_opt(l->stream, o, l->tt, l->nt);
-    launch_prep(l->stream, l->P, l->F, l->d_prep, l->nprep, l->d_norm);
-    launch_conv_prep(l);
 }
 
 template <int CI, int CO, int KS, int S>
@@ -431,23 +363,16 @@ extern "C" {
 int qc_mlearner_create(const qc_mlearner_params* p, int device, qc_mlearner** out) {
     if (!out || !p) return QC_EINVAL;
     *out = nullptr;
-    auto fail = [](const char* m, int rc) { return g_mlearner_err.fail(m, rc); };
+    auto fail = [](const std::string& m, int rc) { return g_mlearner_err.fail(m, rc); };
     if (const char* m = bad_net_size(-1, p->n_actions)) return fail(m, QC_EINVAL);
     if (p->read_length < 1 || p->read_step_length < 1 || p->read_length % p->read_step_length != 0)
         return fail("read_length must be a positive multiple of read_step_length (the reference's view of the "
                     "force channel, RL.py:190-191)", QC_EINVAL);
     const int T1 = conv_out(p->read_length, 13, 5), T2 = conv_out(T1, 11, 4), T3 = conv_out(T2, 9, 4);
     if (T3 < 1) return fail("read_length too short for the three convolutions (T3 < 1)", QC_EINVAL);
-    if (p->batch_size < 128 || p->batch_size > 1024 || p->batch_size % 128 != 0)
-        return fail("batch_size must be a multiple of 128 in [128, 1024]: the learner implements FactorizedNoisy's "
-                    "32-chunk noise branch (layers.py:57-74), not the per-row branch of other batch sizes",
-                    QC_EINVAL);
-    if (p->backup_period < 1) return fail("backup_period must be >= 1", QC_EINVAL);
-    if (!(p->lr >= 0.)) return fail("lr must be >= 0", QC_EINVAL);
-    if (p->target_mode != QC_TD_ALIVE && p->target_mode != QC_TD_REWARD_FAIL && p->target_mode != QC_TD_REWARD)
-        return fail("target_mode must be QC_TD_ALIVE, QC_TD_REWARD_FAIL or QC_TD_REWARD", QC_EINVAL);
-    if (!(p->beta1 >= 0. && p->beta1 < 1.)) return fail("beta1 must be in [0, 1) (0: 0.9)", QC_EINVAL);
-    if (!(p->beta2 >= 0. && p->beta2 < 1.)) return fail("beta2 must be in [0, 1) (0: 0.9995)", QC_EINVAL);
+    const std::string bad =
+        bad_params(1024, p->batch_size, p->backup_period, p->lr, p->target_mode, p->beta1, p->beta2);
+    if (!bad.empty()) return fail(bad, QC_EINVAL);
     if (p->conv_weight_norm != 0 && p->conv_weight_norm != 1)
         return fail("conv_weight_norm must be 0 (plain Conv1d) or 1 (Conv1d_weight_normalize on conv1..3)", QC_EINVAL);
     if ((uint64_t)(64 * T3) * (uint64_t)(3 * p->batch_size) * sizeof(float) >= (1ull << 32))   // 32-bit buffer offsets
@@ -455,128 +380,51 @@ int qc_mlearner_create(const qc_mlearner_params* p, int device, qc_mlearner** ou
     if (const int rc = check_device(device, g_mlearner_err, "the learner")) return rc;
 
     qc_mlearner* l = new qc_mlearner();
-    l->p = *p;
-    l->device = device;
-    l->lr = p->lr;
-    const int L = l->L = p->read_length, A = l->A = p->n_actions, B = l->B = p->batch_size;
+    const int L = l->L = p->read_length, A = p->n_actions, B = p->batch_size;
+    take_params(*l, "qc_mlearner", *p, device, noise_len(kH2, A));
     l->m = p->read_step_length;
-    l->K = L / l->m;
-    l->row_len = L + l->m + l->K + 3;
+    l->Kf = L / l->m;
+    l->row_len = L + l->m + l->Kf + 3;
     l->T[0] = L; l->T[1] = T1; l->T[2] = T2; l->T[3] = T3;
     const int flat = l->flat = 64 * T3;
-    l->b1 = p->beta1 != 0. ? p->beta1 : kBeta1;
-    l->b2 = p->beta2 != 0. ? p->beta2 : kBeta2;
-    l->noise_len = noise_len(kH2, A);
     // padded dY rows: kPad zeros, Tout values, then zeros up to the last q a transposed convolution reads
     for (int j = 1; j <= 3; ++j) {
         const int Qn = (l->T[j - 1] + kS[j - 1] - 1) / kS[j - 1];
         l->Tp[j] = kPad + std::max(l->T[j], Qn);
     }
 
-    // ---- parameter tensors (offsets in multiples of 4 floats)
     const int O[8] = {kC[0], kC[1], kC[2], kH2, kH3, A, kHM, 1};
     const int Kin[8] = {kCI[0] * kKS[0], kCI[1] * kKS[1], kCI[2] * kKS[2], flat, kH2, kH3, kH2, kHM};
     l->cwn = p->conv_weight_norm == 1;
-    int off = 0, nwn = 0, nt = 0;
-    int wn_of[8];
-    auto add = [&](int ti, int n, int kind, int wn, int w_off) {
-        l->tt.t[ti] = Tensor{off, n, kind, wn, w_off};
-        off += (n + 3) & ~3;
-    };
-    for (int j = 0; j < 8; ++j) {
-        const int t0 = l->first[j] = nt;
-        l->wnorm[j] = kWnormTail[j] || (l->cwn && j < 3);
-        nt += kNoisy[j] ? 4 : l->wnorm[j] ? 3 : 2;
-        wn_of[j] = -1;
-        if (kNoisy[j]) {
-            add(t0, O[j] * Kin[j], 0, -1, 0);
-            add(t0 + 1, O[j], 0, -1, 0);
-            add(t0 + 2, O[j] * Kin[j], 0, -1, 0);
-            add(t0 + 3, O[j], 0, -1, 0);
-        } else if (l->wnorm[j]) {
-            wn_of[j] = nwn;
-            l->wn_tensors.t[nwn] = t0;
-            const int w_off = off;
-            add(t0, O[j] * Kin[j], 1, nwn, w_off);
-            add(t0 + 1, O[j], 0, -1, 0);
-            add(t0 + 2, 1, 2, nwn, w_off);
-            ++nwn;
-        } else {
-            add(t0, O[j] * Kin[j], 0, -1, 0);
-            add(t0 + 1, O[j], 0, -1, 0);
-        }
-    }
-    l->np = off;
-    l->nt = nt;
-    l->nwn = nwn;
+    bool wnorm[8];
+    for (int j = 0; j < 8; ++j) wnorm[j] = kWnormTail[j] || (l->cwn && j < 3);
+    build_tensors(*l, 8, O, Kin, kNoisy, wnorm);
     const int* first = l->first;
 
-    // ---- fragment buffer: the forward fragments (the measurement actor's layout; copied to the target), then
-    // the transposed ones
-    int fo = frag_layout(8, O, Kin, kNoisy, l->u8, l->s8, l->ub8, l->sb8);
-    l->nf_fwd = fo;
-    auto tfrag = [&](int rows, int kpad) {   // fragments of a [rows][kpad] matrix
-        const int at = fo;
-        fo += tiles(rows) * ksteps(kpad) * 64;
-        return at;
-    };
-    FragOff& f = l->k.fo;
-    for (int j = 0; j < 4; ++j) {   // the tail's layers in k_learner_fwd's slots fc31, fc41, fc32, fc42
-        f.u[2 + j] = l->u8[4 + j]; f.s[2 + j] = l->s8[4 + j]; f.ub[2 + j] = l->ub8[4 + j]; f.sb[2 + j] = l->sb8[4 + j];
-    }
-    l->tfc1 = tfrag(flat, kH2);
-    f.t31u = tfrag(kH2, kH3);
-    f.t31s = tfrag(kH2, kH3);
-    f.t41u = tfrag(kH3, 32);
-    f.t41s = tfrag(kH3, 32);
-    f.t32 = tfrag(kH2, kHM);
-    f.w42 = fo; fo += kHM;
+    // ---- fragment buffer: the forward fragments (the measurement actor's layout; copied to the target), the
+    // transposed ones of fc1 and the tail, then the convolutions' per-phase ones (and effective weights)
+    build_tail_frags(*l, Kin, 3, 3);
     int cfrag_n[3] = {0, 0, 0};
     for (int j = 1; j < 3; ++j) {
         const int NI = (kKS[j] + kS[j] - 1) / kS[j];
         cfrag_n[j] = kS[j] * (kCI[j] / 32) * (NI * kC[j] / 2) * 64;
-        l->tconv[j] = fo;
-        fo += cfrag_n[j];
+        l->tconv[j] = l->nf;
+        l->nf += cfrag_n[j];
     }
-    if (l->cwn)
-        for (int j = 0; j < 3; ++j) {
-            l->weff[j] = fo;
-            fo += (kC[j] * Kin[j] + 3) & ~3;
-        }
-    l->nf = fo;
-
-    std::vector<PrepJob> prep;
-    for (int j = 3; j < 8; ++j) {
-        const Tensor* T = &l->tt.t[first[j]];
-        const int g_off = l->wnorm[j] ? T[2].off : -1;
-        prep.push_back(PrepJob{T[0].off, g_off, wn_of[j], O[j], Kin[j], 0, Kin[j], l->u8[j], T[1].off, l->ub8[j]});
-        if (kNoisy[j])
-            prep.push_back(PrepJob{T[2].off, -1, -1, O[j], Kin[j], 0, Kin[j], l->s8[j], T[3].off, l->sb8[j]});
-    }
-    auto tjob = [&](int j, int sigma, int kpad, int out_off) {
-        const Tensor* T = &l->tt.t[first[j]];
-        prep.push_back(PrepJob{T[sigma ? 2 : 0].off, l->wnorm[j] ? T[2].off : -1, -1, O[j], Kin[j], 1, kpad, out_off, -1, -1});
-    };
-    tjob(3, 0, kH2, l->tfc1);
-    tjob(4, 0, kH3, f.t31u);
-    tjob(4, 1, kH3, f.t31s);
-    tjob(5, 0, 32, f.t41u);
-    tjob(5, 1, 32, f.t41s);
-    tjob(6, 0, kHM, f.t32);
-    prep.push_back(PrepJob{l->tt.t[first[7]].off, l->tt.t[first[7] + 2].off, -1, 1, kHM, 2, kHM, f.w42, -1, -1});
     // weight-normalised convolutions: the effective weights in the natural layout (and the norms for the optimizer);
     // k_mlearner_prep, launched after k_learner_prep, makes the fragments from them
     if (l->cwn)
         for (int j = 0; j < 3; ++j) {
+            l->weff[j] = l->nf;
+            l->nf += (kC[j] * Kin[j] + 3) & ~3;
             const Tensor* T = &l->tt.t[first[j]];
-            prep.push_back(PrepJob{T[0].off, T[2].off, wn_of[j], kC[j], Kin[j], 2, Kin[j], l->weff[j], -1, -1});
+            l->prep.push_back(PrepJob{T[0].off, T[2].off, l->wn_of[j], kC[j], Kin[j], 2, Kin[j], l->weff[j], -1, -1});
         }
-    l->nprep = (int)prep.size();
     int cmax = 0;
     auto conv_w = [&](int j) { return l->cwn ? l->weff[j] : l->tt.t[first[j]].off; };   // offset from k_mlearner_prep's Wb
     for (int j = 0; j < 3; ++j) {
         const int n = tiles(kC[j]) * (Kin[j] / 2) * 64;
-        l->cprep.j[j] = ConvPrepJob{conv_w(j), l->tt.t[first[j] + 1].off, l->u8[j], l->ub8[j],
+        l->cprep.j[j] = ConvPrepJob{conv_w(j), l->tt.t[first[j] + 1].off, l->u[j], l->ub[j],
                                     kC[j], kCI[j], kKS[j], kS[j], 0, n};
         cmax = std::max(cmax, n);
     }
@@ -594,19 +442,9 @@ int qc_mlearner_create(const qc_mlearner_params* p, int device, qc_mlearner** ou
         l->nchunks[j] = B / l->epc[j] * l->nseg[j];
     }
 
-    // ---- workspace (floats): every feature-major array has its rows padded to 32 and its pad rows zero
-    size_t w = 0;
-    auto take = [&](size_t n) {
-        const size_t at = w;
-        w += (n + 3) & ~(size_t)3;
-        return at;
-    };
+    // ---- workspace: behind the shared head, the convolutional stack's arrays
+    Carve take{tail_workspace(*l, kH2, 0, nullptr)};
     const size_t Bs = (size_t)B;
-    const size_t oQ = take(3 * Bs * 32), oM = take(3 * Bs), oN = take((size_t)l->noise_len * kChunks);
-    const size_t oH2 = take(kH2 * Bs), oH2e = take(kH2 * Bs), oA3 = take(kH3 * Bs), oA3e = take(kH3 * Bs),
-                 oR32 = take(kHM * Bs), odQ = take(32 * Bs), odQe = take(32 * Bs), odM = take(32 * Bs),
-                 odZ3 = take(kH3 * Bs), odZ3e = take(kH3 * Bs), odZ32 = take(kHM * Bs), odZ2 = take(kH2 * Bs);
-    const size_t oLoss = take(4), oNorm = take(kMaxWN);
     const size_t oX = take(2 * Bs * 2 * L);
     size_t oy[4] = {0, 0, 0, 0}, ody[4] = {0, 0, 0, 0}, opart[3], opartb[3];
     for (int j = 1; j <= 3; ++j) oy[j] = take(3 * Bs * kC[j - 1] * l->T[j]);
@@ -618,33 +456,14 @@ int qc_mlearner_create(const qc_mlearner_params* p, int device, qc_mlearner** ou
     }
 
     Dev g(device);
-    hipError_t e = hipSuccess;
-    for (float** q : {&l->P, &l->PT, &l->G, &l->E, &l->V, &l->MU})
-        if (e == hipSuccess) e = dalloc(l, q, (size_t)l->np);
-    if (e == hipSuccess) e = dalloc(l, &l->F, (size_t)l->nf);
-    if (e == hipSuccess) e = dalloc(l, &l->FT, (size_t)l->nf_fwd);
-    if (e == hipSuccess) e = dalloc(l, &l->ws, w);
-    if (e == hipSuccess) e = dalloc(l, &l->d_dot, 2 * kMaxWN);
-    if (e == hipSuccess) e = dalloc(l, &l->d_cnt, 2);
-    if (e == hipSuccess) e = dalloc(l, &l->d_prep, prep.size());
-    if (e == hipSuccess) e = hipMemcpy(l->d_prep, prep.data(), prep.size() * sizeof(PrepJob), hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        free_all(l);
+    if (alloc_core(*l, kH2, 0, take.w) != hipSuccess) {
+        free_all(*l);
         delete l;
         return fail("device allocation failed", QC_ENOMEM);
     }
     float* W = l->ws;
     LArgs& k = l->k;
-    k.F = l->F;
-    k.FT = l->FT;
-    k.in_len = 0; k.in_pad = 0; k.n_act = A; k.B = B; k.row_len = l->row_len; k.rpc = B / kChunks;
-    k.noise = l->d_noise = W + oN;
-    k.Q = W + oQ; k.M = W + oM;
-    k.H2 = W + oH2; k.H2e = W + oH2e; k.A3 = W + oA3; k.A3e = W + oA3e; k.R32 = W + oR32;
-    k.dQ = W + odQ; k.dQe = W + odQe; k.dM = W + odM; k.dZ3 = W + odZ3; k.dZ3e = W + odZ3e; k.dZ32 = W + odZ32;
-    k.dZ2 = W + odZ2;
-    l->d_loss = W + oLoss;
-    l->d_norm = W + oNorm;
+    k.in_len = 0; k.in_pad = 0; k.row_len = l->row_len;
     l->X = W + oX;
     for (int j = 1; j <= 3; ++j) {
         l->y[j] = W + oy[j];
@@ -653,16 +472,15 @@ int qc_mlearner_create(const qc_mlearner_params* p, int device, qc_mlearner** ou
     l->y3f = W + oy3f; l->h1 = W + oh1; l->y3p = W + oy3p;
     k.h_in = l->h1;
     k.h_ld = 3 * B;
-    float* G = l->G;
-    auto gt = [&](int ti) { return G + l->tt.t[ti].off; };
+    auto gt = [&](int j, int i) { return l->G + l->tt.t[first[j] + i].off; };
     for (int j = 0; j < 3; ++j) {
         l->part[j] = W + opart[j];
         l->partb[j] = W + opartb[j];
     }
     int blk = 0;
     for (int j = 0; j < 3; ++j) {
-        l->red.j[2 * j] = RedJob{l->part[j], gt(first[j]), kC[j] * Kin[j], l->nchunks[j]};
-        l->red.j[2 * j + 1] = RedJob{l->partb[j], gt(first[j] + 1), kC[j], l->nchunks[j]};
+        l->red.j[2 * j] = RedJob{l->part[j], gt(j, 0), kC[j] * Kin[j], l->nchunks[j]};
+        l->red.j[2 * j + 1] = RedJob{l->partb[j], gt(j, 1), kC[j], l->nchunks[j]};
         for (int q = 0; q < 2; ++q) {
             l->red.first_block[2 * j + q] = blk;
             blk += (l->red.j[2 * j + q].n + 31) / 32;
@@ -670,25 +488,15 @@ int qc_mlearner_create(const qc_mlearner_params* p, int device, qc_mlearner** ou
     }
     l->red.first_block[6] = blk;
 
-    // ---- the dense dW jobs and their tiles (dY, X, gradient tensor, bias gradient tensor)
-    const int t1 = first[3], t21 = first[4], t31 = first[5], t22 = first[6], t32 = first[7];
+    // ---- the dense dW jobs (dY, X, gradient tensor, bias gradient tensor)
     const DwJob jobs[7] = {
-        {k.dZ2, l->y3p, gt(t1), gt(t1 + 1), kH2, flat},        {k.dZ3, k.H2, gt(t21), gt(t21 + 1), kH3, kH2},
-        {k.dZ3e, k.H2e, gt(t21 + 2), gt(t21 + 3), kH3, kH2},   {k.dQ, k.A3, gt(t31), gt(t31 + 1), A, kH3},
-        {k.dQe, k.A3e, gt(t31 + 2), gt(t31 + 3), A, kH3},      {k.dZ32, k.H2, gt(t22), gt(t22 + 1), kHM, kH2},
-        {k.dM, k.R32, gt(t32), gt(t32 + 1), 1, kHM},
+        {k.dZ2, l->y3p, gt(3, 0), gt(3, 1), kH2, flat},   {k.dZ3, k.H2, gt(4, 0), gt(4, 1), kH3, kH2},
+        {k.dZ3e, k.H2e, gt(4, 2), gt(4, 3), kH3, kH2},    {k.dQ, k.A3, gt(5, 0), gt(5, 1), A, kH3},
+        {k.dQe, k.A3e, gt(5, 2), gt(5, 3), A, kH3},       {k.dZ32, k.H2, gt(6, 0), gt(6, 1), kHM, kH2},
+        {k.dM, k.R32, gt(7, 0), gt(7, 1), 1, kHM},
     };
-    std::vector<int4> tl;
-    for (int j = 0; j < 7; ++j)
-        for (int to = 0; to < tiles(jobs[j].O); ++to)
-            for (int tk = 0; tk < tiles(jobs[j].K); ++tk) tl.push_back(int4{j, to, tk, 0});
-    l->ntiles = (int)tl.size();
-    e = dalloc(l, &l->d_dwjobs, 7);
-    if (e == hipSuccess) e = hipMemcpy(l->d_dwjobs, jobs, sizeof(jobs), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = dalloc(l, &l->d_tiles, tl.size());
-    if (e == hipSuccess) e = hipMemcpy(l->d_tiles, tl.data(), tl.size() * sizeof(int4), hipMemcpyHostToDevice);
-    if (e != hipSuccess || !enable_mtail_lds()) {
-        free_all(l);
+    if (upload_dw(*l, jobs, 7) != hipSuccess || !enable_mtail_lds()) {
+        free_all(*l);
         delete l;
         return fail("device setup failed (job tables / LDS size of the learner kernels)", QC_EHIP);
     }
@@ -698,11 +506,7 @@ int qc_mlearner_create(const qc_mlearner_params* p, int device, qc_mlearner** ou
 
 void qc_mlearner_destroy(qc_mlearner* l) {
     if (!l) return;
-    {
-        Dev g(l->device);
-        (void)hipDeviceSynchronize();
-        free_all(l);
-    }
+    destroy_core(*l);
     delete l;
 }
 
@@ -718,6 +522,7 @@ int qc_mlearner_noise_len(const qc_mlearner* l) { return l ? l->noise_len : QC_E
 
 int qc_mlearner_load(qc_mlearner* l, const qc_dqn_layer layers[8]) {
     if (!l || !layers) return QC_EINVAL;
+    // not validate_layers / LayerRule (qcart_host.hpp): these texts name the layer, and conv1..3's depend on the handle
     for (int j = 0; j < 8; ++j) {
         const qc_dqn_layer& Y = layers[j];
         if (!Y.weight || !Y.bias) {
@@ -753,63 +558,32 @@ int qc_mlearner_load(qc_mlearner* l, const qc_dqn_layer layers[8]) {
         }
     }
     Dev g(l->device);
-    hipError_t e = hipSuccess;
-    auto put = [&](int ti, const float* src) {
-        const Tensor& T = l->tt.t[ti];
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(l->P + T.off, src, (size_t)T.n * sizeof(float), hipMemcpyDeviceToDevice, l->stream);
-    };
-    for (int j = 0; j < 8; ++j) {
-        const qc_dqn_layer& Y = layers[j];
-        put(l->first[j], Y.weight);
-        put(l->first[j] + 1, Y.bias);
-        if (kNoisy[j]) {
-            put(l->first[j] + 2, Y.sigma_w);
-            put(l->first[j] + 3, Y.sigma_b);
-        } else if (l->wnorm[j]) {
-            put(l->first[j] + 2, Y.weight_norm);
-        }
-    }
-    const size_t pb = (size_t)l->np * sizeof(float);
-    for (float* q : {l->E, l->V, l->MU, l->G})
-        if (e == hipSuccess) e = hipMemsetAsync(q, 0, pb, l->stream);
-    if (e != hipSuccess) return hip_fail(l->err, e, "learner parameter copy");
-    launch_prep(l->stream, l->P, l->F, l->d_prep, l->nprep, l->d_norm);
+    if (const int rc = load_core(*l, layers)) return rc;
     launch_conv_prep(l);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(l->err, e, "learner weight preparation");
-    l->step = 0;
-    l->l1 = l->l2 = 0.;
-    l->backup_counter = 0;
-    l->loaded = true;
-    return QC_OK;
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? QC_OK : hip_fail(l->err, e, "learner weight preparation");
 }
 
 int qc_mlearner_layers(qc_mlearner* l, int target, qc_dqn_layer out[8]) {
     if (!l || !out) return QC_EINVAL;
-    layer_views(l, target ? l->PT : l->P, out);
+    layer_views(*l, target ? l->PT : l->P, out);
     return QC_OK;
 }
 
 int qc_mlearner_grads(qc_mlearner* l, qc_dqn_layer out[8]) {
     if (!l || !out) return QC_EINVAL;
-    layer_views(l, l->G, out);
+    layer_views(*l, l->G, out);
     return QC_OK;
 }
 
-int qc_mlearner_set_lr(qc_mlearner* l, double lr) {
-    if (!l) return QC_EINVAL;
-    if (!(lr >= 0.)) { l->err = "lr must be >= 0"; return QC_EINVAL; }
-    l->lr = lr;
-    return QC_OK;
-}
+int qc_mlearner_set_lr(qc_mlearner* l, double lr) { return l ? set_lr(*l, lr) : QC_EINVAL; }
 
 int qc_mlearner_states(qc_mlearner* l, const float* transitions, float* next_out, float* prev_out) {
     if (!l || !transitions || !next_out || !prev_out) return QC_EINVAL;
     Dev g(l->device);
     const size_t n = (size_t)l->B * 2 * l->L;
-    hipLaunchKernelGGL(k_mlearner_states, dim3(l->B), dim3(256), (l->K + 1) * sizeof(float), l->stream, transitions, l->X,
-                       l->L, l->m, l->K, l->row_len, l->B);
+    hipLaunchKernelGGL(k_mlearner_states, dim3(l->B), dim3(256), (l->Kf + 1) * sizeof(float), l->stream, transitions, l->X,
+                       l->L, l->m, l->Kf, l->row_len, l->B);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipMemcpyAsync(next_out, l->X, n * sizeof(float), hipMemcpyDeviceToDevice, l->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(prev_out, l->X + n, n * sizeof(float), hipMemcpyDeviceToDevice, l->stream);
@@ -820,28 +594,12 @@ int qc_mlearner_states(qc_mlearner* l, const float* transitions, float* next_out
 int qc_mlearner_update(qc_mlearner* l, const float* transitions, const float* is_weights, const float* noise,
                        uint64_t counter, float* unweighted_loss, float* loss) {
     if (!l) return QC_EINVAL;
-    if (!l->loaded) { l->err = "qc_mlearner_load has not been called"; return QC_EINVAL; }
-    if (!transitions || !is_weights || !unweighted_loss) {
-        l->err = "transitions, is_weights and unweighted_loss are required";
-        return QC_EINVAL;
-    }
     Dev g(l->device);
+    if (const int rc = begin_update(*l, transitions, is_weights, unweighted_loss, noise, counter)) return rc;
     hipStream_t s = l->stream;
-    int launches = 0;
-    // the target network follows the online one every backup_period updates (RL.py:164-169)
-    if (l->backup_counter == 0) {
-        hipError_t e = hipMemcpyAsync(l->PT, l->P, (size_t)l->np * sizeof(float), hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(l->FT, l->F, (size_t)l->nf_fwd * sizeof(float), hipMemcpyDeviceToDevice, s);
-        if (e != hipSuccess) return hip_fail(l->err, e, "target network copy");
-        launches += 2;
-    }
-    l->backup_counter = (l->backup_counter + 1) % l->p.backup_period;
-
     const int B = l->B, L = l->L;
-    launch_noise(s, noise, l->d_noise, l->noise_len, l->p.seed, counter);
-    hipLaunchKernelGGL(k_mlearner_states, dim3(B), dim3(256), (l->K + 1) * sizeof(float), s, transitions, l->X, L, l->m,
-                       l->K, l->row_len, B);
+    hipLaunchKernelGGL(k_mlearner_states, dim3(B), dim3(256), (l->Kf + 1) * sizeof(float), s, transitions, l->X, L, l->m,
+                       l->Kf, l->row_len, B);
     // ---- forward: the online net on next | prev (envs 0 .. 2B), the target net on next (envs 2B .. 3B)
     for (int tgt = 0; tgt < 2; ++tgt) {
         const float* Fw = tgt ? l->FT : l->F;
@@ -850,8 +608,8 @@ int qc_mlearner_update(qc_mlearner* l, const float* transitions, const float* is
         a.x = l->X;
         a.L = L; a.T1 = l->T[1]; a.T2 = l->T[2]; a.T3 = l->T[3];
         for (int j = 0; j < 4; ++j) {
-            a.wf[j] = Fw + l->u8[j];
-            a.bias[j] = Fw + l->ub8[j];
+            a.wf[j] = Fw + l->u[j];
+            a.bias[j] = Fw + l->ub[j];
         }
         a.y1 = l->y[1] + e0 * kC[0] * l->T[1];
         a.y2 = l->y[2] + e0 * kC[1] * l->T[2];
@@ -867,25 +625,13 @@ int qc_mlearner_update(qc_mlearner* l, const float* transitions, const float* is
     LArgs k = l->k;
     k.trans = transitions;
     launch_mtail_fwd(s, k);
-    LossArgs a{};
-    a.Q = k.Q; a.M = k.M; a.w = is_weights; a.noise = l->d_noise;
     // k_learner_loss reads the action at row[2 in_len] and the reward after it: in_len = 0 on rows that start
     // at the action column
-    a.trans = transitions + (l->row_len - 2);
-    a.B = B; a.n_act = l->A; a.in_len = 0; a.row_len = l->row_len; a.rpc = k.rpc;
-    a.eps_out41 = kH2 + 2 * kH3;
-    a.omg = (float)(1. - l->p.gamma);
-    a.gamma = (float)l->p.gamma;
-    a.rew = (float)((1. - l->p.gamma) * l->p.alive_reward);
-    a.failing = (float)l->p.failing_reward;
-    a.inv_B = (float)(1. / B);
-    a.inv_A = (float)(1. / l->A);
-    a.dQ = k.dQ; a.dQe = k.dQe; a.dM = k.dM; a.ul = unweighted_loss; a.loss = l->d_loss; a.loss_user = loss;
-    a.cnt = l->d_cnt;
-    launch_loss(s, l->p.target_mode, a);
+    launch_loss(s, l->target_mode,
+                loss_args(*l, transitions + (l->row_len - 2), 0, kH2, is_weights, unweighted_loss, loss));
     launch_mtail_bwd(s, k);
     // ---- backward of fc1 and of the convolutions
-    hipLaunchKernelGGL(k_mlearner_fc1t, dim3(B / kE, (tiles(l->flat) + 7) / 8), dim3(kThreads), 0, s, l->F + l->tfc1, k.dZ2,
+    hipLaunchKernelGGL(k_mlearner_fc1t, dim3(B / kE, (tiles(l->flat) + 7) / 8), dim3(kThreads), 0, s, l->F + k.fo.t2, k.dZ2,
                        l->y3p, l->dY[3], l->T[3], l->Tp[3], l->flat, B);
     launch_convt<64, 64, 9, 4>(l, 2);
     launch_convt<32, 64, 11, 4>(l, 1);
@@ -895,67 +641,21 @@ int qc_mlearner_update(qc_mlearner* l, const float* transitions, const float* is
     hipLaunchKernelGGL(k_mlearner_reduce, dim3(l->red.first_block[6]), dim3(256), 0, s, l->red);
     launch_dw(s, l->d_dwjobs, l->d_tiles, l->ntiles, B);
     launch_wndot(s, l->nwn, l->P, l->G, l->wn_tensors, l->tt, l->d_dot);
-    optimizer_and_prep(l, 1);
-    launches += 28;
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(l->err, e, "learner update launch");
-    l->updates += 1;
-    l->launches = launches;
-    return QC_OK;
+    opt_step(*l, 1);
+    launch_conv_prep(l);
+    return end_update(*l, 28);
 }
 
 int qc_mlearner_apply(qc_mlearner* l, const qc_dqn_layer grads[8]) {
     if (!l || !grads) return QC_EINVAL;
-    if (!l->loaded) { l->err = "qc_mlearner_load has not been called"; return QC_EINVAL; }
     Dev g(l->device);
-    hipError_t e = hipSuccess;
-    auto put = [&](int ti, const float* src) {
-        const Tensor& T = l->tt.t[ti];
-        if (!src) { l->err = "every gradient tensor is required"; e = hipErrorInvalidValue; return; }
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(l->G + T.off, src, (size_t)T.n * sizeof(float), hipMemcpyDeviceToDevice, l->stream);
-    };
-    for (int j = 0; j < 8 && e == hipSuccess; ++j) {
-        const qc_dqn_layer& Y = grads[j];
-        put(l->first[j], Y.weight);
-        put(l->first[j] + 1, Y.bias);
-        if (kNoisy[j]) {
-            put(l->first[j] + 2, Y.sigma_w);
-            put(l->first[j] + 3, Y.sigma_b);
-        } else if (l->wnorm[j]) {
-            put(l->first[j] + 2, Y.weight_norm);
-        }
-    }
-    if (e == hipErrorInvalidValue) return QC_EINVAL;
-    if (e != hipSuccess) return hip_fail(l->err, e, "learner gradient copy");
-    optimizer_and_prep(l, 0);
-    e = hipGetLastError();
-    if (e != hipSuccess) return hip_fail(l->err, e, "learner optimizer launch");
-    return QC_OK;
+    if (const int rc = apply_core(*l, grads)) return rc;
+    launch_conv_prep(l);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? QC_OK : hip_fail(l->err, e, "learner optimizer launch");
 }
 
-int qc_mlearner_stats(qc_mlearner* l, qc_learner_stats_t* out) {
-    if (!l || !out) return QC_EINVAL;
-    Dev g(l->device);
-    int32_t cnt[2] = {0, 0};
-    hipError_t e = hipStreamSynchronize(l->stream);
-    if (e == hipSuccess) e = hipMemcpy(cnt, l->d_cnt, sizeof(cnt), hipMemcpyDeviceToHost);
-    if (e != hipSuccess) return hip_fail(l->err, e, "learner stats");
-    out->updates = l->updates;
-    out->step = l->step;
-    out->backup_counter = l->backup_counter;
-    out->launches_per_update = l->launches;
-    out->l1 = l->l1;
-    out->l2 = l->l2;
-    out->lr = l->lr;
-    out->nonfinite = cnt[0];
-    if (cnt[1]) {
-        const int32_t zero = 0;
-        (void)hipMemcpy(l->d_cnt + 1, &zero, sizeof(zero), hipMemcpyHostToDevice);
-        l->err = "an update since the last qc_mlearner_stats saw an action outside [0, n_actions) (clamped on the device)";
-        return QC_EINVAL;
-    }
-    return QC_OK;
-}
+int qc_mlearner_stats(qc_mlearner* l, qc_learner_stats_t* out) { return l && out ? stats_core(*l, out) : QC_EINVAL; }
 
 }  // extern "C"
+

@@ -49,30 +49,31 @@ def _shapes(data_length: int, n_actions: int, hidden2: int = 256):
     return ((512, data_length), (hidden2, 512), (256, hidden2), (n_actions, 256), (128, hidden2), (1, 128))
 
 
-class DQNLearner(L.DeviceHandle):
-    """TrainDQN for direct_DQN(data_length, noisy_layers=2) with LaProp(centered, betas); hidden2 (None: from
-    `fc2.weight`), target and betas select the driver (module docstring)."""
+class _Learner(L.DeviceHandle):
+    """What the two learners share over one libqcart handle family `_prefix`: the constructor's checks, and every
+    call that differs between them only in that prefix. A subclass supplies `_prefix`, `_n_layers`, `_max_batch`,
+    `_layer_array`, `_tensors` and `push`, and sets `batch_size`, `row_len` and `n_actions` before `_create`."""
 
-    _prefix = "qc_learner"
+    _n_layers = 0
+    _max_batch = 0
 
-    def __init__(self, params: Mapping[str, torch.Tensor], batch_size: int = 512, gamma: float = 0.998,
-                 lr: float = 4e-4, alive_reward: float = 10., failing_reward: float = -1., backup_period: int = 300,
-                 device: int | str | torch.device = 0, seed: int = 0, data_length: Optional[int] = None,
-                 n_actions: Optional[int] = None, hidden2: Optional[int] = None, target: str = "alive",
-                 betas=(0.9, 0.9995)):
+    def _fn(self, name: str):
+        return getattr(L.lib(), f"{self._prefix}_{name}")
+
+    def _layers(self):
+        return (L.QcDqnLayer * self._n_layers)()
+
+    def _resolve(self, device, batch_size: int):
         self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         if self.device.type != "cuda":
-            raise RuntimeError("DQNLearner runs on a HIP device only (no CPU fallback)")
+            raise RuntimeError(f"{type(self).__name__} runs on a HIP device only (no CPU fallback)")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
-        if batch_size % 128 != 0 or not 128 <= batch_size <= 4096:
-            raise ValueError("batch_size must be a multiple of 128 in [128, 4096] (FactorizedNoisy's 32-chunk "
-                             "noise branch; the per-row branch of other sizes is not implemented)")
-        if "fc1.weight" not in params or "fc41.u_w" not in params:
-            raise ValueError("params must be a direct_DQN(noisy_layers=2) state_dict (fc1.weight, ..., fc41.u_w)")
-        if "fc2.weight" not in params:
-            raise ValueError("params must be a direct_DQN(noisy_layers=2) state_dict (fc2.weight is missing)")
-        self.hidden2 = fc2_width(params, hidden2)
+        if batch_size % 128 != 0 or not 128 <= batch_size <= self._max_batch:
+            raise ValueError(f"batch_size must be a multiple of 128 in [128, {self._max_batch}] (FactorizedNoisy's "
+                             "32-chunk noise branch; the per-row branch of other sizes is not implemented)")
+
+    def _schedule(self, target: str, betas):
         if target not in L.TD_TARGETS:
             raise ValueError(f"target must be one of {sorted(L.TD_TARGETS)}, not {target!r}")
         self.target = target
@@ -80,29 +81,148 @@ class DQNLearner(L.DeviceHandle):
         for name, b in zip(("beta1", "beta2"), self.betas):
             if not 0. < b < 1.:
                 raise ValueError(f"{name} (betas) must be in (0, 1), not {b}")
-        self.data_length = int(data_length if data_length is not None else params["fc1.weight"].shape[1])
-        self.n_actions = int(n_actions if n_actions is not None else params["fc41.u_w"].shape[0])
-        self.batch_size = int(batch_size)
-        self.row_len = 2 * self.data_length + 2
-        p = L.QcLearnerParams()
-        p.data_length, p.n_actions, p.batch_size = self.data_length, self.n_actions, self.batch_size
-        p.backup_period, p.gamma, p.lr = int(backup_period), float(gamma), float(lr)
+
+    def _create(self, p, params, gamma, lr, alive_reward, failing_reward, backup_period, seed):
+        """Fill the fields the two params structs share, create the handle and load `params`."""
+        p.n_actions, p.batch_size = self.n_actions, self.batch_size
+        p.backup_period, p.target_mode = int(backup_period), L.TD_TARGETS[self.target]
+        p.gamma, p.lr = float(gamma), float(lr)
         p.alive_reward, p.failing_reward, p.seed = float(alive_reward), float(failing_reward), int(seed)
-        p.hidden2, p.target_mode = self.hidden2, L.TD_TARGETS[target]
         p.beta1, p.beta2 = self.betas
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             torch.cuda.init()
-            self._check(L.lib().qc_learner_create(ctypes.byref(p), self.device.index, ctypes.byref(h)))
+            self._check(self._fn("create")(ctypes.byref(p), self.device.index, ctypes.byref(h)))
         self._h = h
-        self.noise_len = int(L.lib().qc_learner_noise_len(h))
+        self.noise_len = int(self._fn("noise_len")(h))
         self.counter = 0
         self.last_loss = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._keep = []
         self.load_state_dict(params)
 
+    def _send(self, fn: str, params: Mapping[str, torch.Tensor]):
+        layers, keep = self._layer_array(params)
+        with torch.cuda.device(self.device):
+            self._bind_stream()
+            self._check(self._fn(fn)(self._h, layers))
+        self._keep = keep   # the copies read them on the current stream
+
+    def load_state_dict(self, params: Mapping[str, torch.Tensor]):
+        """Load the layers from a state_dict (the reference net's, or actor.random_direct_dqn's /
+        actor.random_dqn_measurement's; a MeasurementLearner's must have the handle's kind of convolutions);
+        resets the optimizer state and the target schedule."""
+        self._send("load", params)
+
+    def _copies(self, fn: str, *args) -> dict:
+        layers = self._layers()
+        self._check(self._fn(fn)(self._h, *args, layers))
+        with torch.cuda.device(self.device):
+            return {k: v.clone() for k, v in self._tensors(layers).items()}
+
+    def state_dict(self, target: bool = False) -> dict:
+        """The online (or target) parameters under the reference's key names, as device copies."""
+        return self._copies("layers", 1 if target else 0)
+
+    def grads(self) -> dict:
+        """Gradients of the last update under the parameters' key names (weight_norm: dg), as device copies."""
+        return self._copies("grads")
+
+    def apply(self, grads: Mapping[str, torch.Tensor]):
+        """One LaProp step on injected gradients (tests)."""
+        self._send("apply", grads)
+
+    def set_lr(self, lr: float):
+        self._check(self._fn("set_lr")(self._h, float(lr)))
+
+    def _rows(self, transitions: torch.Tensor) -> torch.Tensor:
+        if transitions.dim() != 2 or tuple(transitions.shape) != (self.batch_size, self.row_len):
+            raise ValueError(f"transitions must be [{self.batch_size}, {self.row_len}]")
+        return transitions.to(device=self.device, dtype=torch.float32).contiguous()
+
+    def update(self, transitions: torch.Tensor, is_weights: torch.Tensor, noise: Optional[torch.Tensor] = None,
+               counter: Optional[int] = None) -> torch.Tensor:
+        """One update on transitions [batch_size, row_len] (DQNLearner: row_len = 2 data_length + 2;
+        MeasurementLearner: rows of MeasurementRecord) and IS weights [batch_size]. noise: optional
+        [32, noise_len], already f-transformed, the actor's layout per chunk; else Philox (seed, chunk, counter).
+        Returns unweighted_loss [batch_size] (device); the scalar loss stays in `last_loss` (device).
+        Asynchronous: an action outside [0, n_actions) is clamped and raised by the next `stats()`."""
+        tr = self._rows(transitions)
+        if is_weights.numel() != self.batch_size:
+            raise ValueError(f"is_weights must be [{self.batch_size}]")
+        w = is_weights.to(device=self.device, dtype=torch.float32).contiguous()
+        nz = None
+        if noise is not None:
+            if tuple(noise.shape) != (32, self.noise_len):
+                raise ValueError(f"noise must be [32, {self.noise_len}]")
+            nz = noise.to(device=self.device, dtype=torch.float32).contiguous()
+        if counter is None:
+            counter = self.counter
+            self.counter += 1
+        ul = torch.empty(self.batch_size, dtype=torch.float32, device=self.device)
+        vp = ctypes.c_void_p
+        with torch.cuda.device(self.device):
+            self._bind_stream()
+            self._check(self._fn("update")(
+                self._h, vp(tr.data_ptr()), vp(w.data_ptr()), vp(nz.data_ptr()) if nz is not None else None,
+                int(counter), vp(ul.data_ptr()), vp(self.last_loss.data_ptr())))
+        return ul
+
+    def step(self, memory, counter: Optional[int] = None):
+        """TrainDQN.__call__: obtain_sample -> update -> memory.batch_update(tree_idx, unweighted_loss). None
+        while len(memory) < batch_size (RL.py:161)."""
+        smp = memory.obtain_sample(self.batch_size)
+        if smp is None:
+            return None
+        tree_idx, is_weights, transitions = smp
+        ul = self.update(transitions, is_weights, counter=counter)
+        memory.batch_update(tree_idx, ul)
+        return ul
+
+    def _push(self, actor, load, check):
+        """The online layers into an actor handle through `load`, device to device (no host copy)."""
+        layers = self._layers()
+        self._check(self._fn("layers")(self._h, 0, layers))
+        with torch.cuda.device(self.device):
+            actor._bind_stream()
+            check(load(actor._h, layers), actor._h)
+
+    def stats(self) -> dict:
+        """Synchronises. Raises QCartError if an update since the last call saw an out-of-range action."""
+        s = L.QcLearnerStats()
+        self._check(self._fn("stats")(self._h, ctypes.byref(s)))
+        return {k: getattr(s, k) for k, _ in L.QcLearnerStats._fields_}
+
+
+class DQNLearner(_Learner):
+    """TrainDQN for direct_DQN(data_length, noisy_layers=2) with LaProp(centered, betas); hidden2 (None: from
+    `fc2.weight`), target and betas select the driver (module docstring)."""
+
+    _prefix = "qc_learner"
+    _n_layers = 6
+    _max_batch = 4096
+
+    def __init__(self, params: Mapping[str, torch.Tensor], batch_size: int = 512, gamma: float = 0.998,
+                 lr: float = 4e-4, alive_reward: float = 10., failing_reward: float = -1., backup_period: int = 300,
+                 device: int | str | torch.device = 0, seed: int = 0, data_length: Optional[int] = None,
+                 n_actions: Optional[int] = None, hidden2: Optional[int] = None, target: str = "alive",
+                 betas=(0.9, 0.9995)):
+        self._resolve(device, batch_size)
+        if "fc1.weight" not in params or "fc41.u_w" not in params:
+            raise ValueError("params must be a direct_DQN(noisy_layers=2) state_dict (fc1.weight, ..., fc41.u_w)")
+        if "fc2.weight" not in params:
+            raise ValueError("params must be a direct_DQN(noisy_layers=2) state_dict (fc2.weight is missing)")
+        self.hidden2 = fc2_width(params, hidden2)
+        self._schedule(target, betas)
+        self.data_length = int(data_length if data_length is not None else params["fc1.weight"].shape[1])
+        self.n_actions = int(n_actions if n_actions is not None else params["fc41.u_w"].shape[0])
+        self.batch_size = int(batch_size)
+        self.row_len = 2 * self.data_length + 2
+        p = L.QcLearnerParams()
+        p.data_length, p.hidden2 = self.data_length, self.hidden2
+        self._create(p, params, gamma, lr, alive_reward, failing_reward, backup_period, seed)
+
     def _layer_array(self, params: Mapping[str, torch.Tensor]):
-        layers = (L.QcDqnLayer * 6)()
+        layers = self._layers()
         keep = []
         for i, (name, shape) in enumerate(zip(LAYERS, _shapes(self.data_length, self.n_actions, self.hidden2))):
             if NOISY[i] != (f"{name}.u_w" in params):
@@ -113,15 +233,6 @@ class DQNLearner(L.DeviceHandle):
             keep += t
             L.fill_layer(layers[i], t)
         return layers, keep
-
-    def load_state_dict(self, params: Mapping[str, torch.Tensor]):
-        """Load the six layers from a state_dict (a reference direct_DQN's, or actor.random_direct_dqn's);
-        resets the optimizer state and the target schedule."""
-        layers, keep = self._layer_array(params)
-        with torch.cuda.device(self.device):
-            self._bind_stream()
-            self._check(L.lib().qc_learner_load(self._h, layers))
-        self._keep = keep   # the copies read them on the current stream
 
     def _tensors(self, layers) -> dict:
         out = {}
@@ -138,71 +249,6 @@ class DQNLearner(L.DeviceHandle):
                 out[f"{name}.weight_norm"] = _view(ly.weight_norm, 1, torch.float32, self.device).view(())
         return out
 
-    def state_dict(self, target: bool = False) -> dict:
-        """The online (or target) parameters under the reference's key names, as device copies."""
-        layers = (L.QcDqnLayer * 6)()
-        self._check(L.lib().qc_learner_layers(self._h, 1 if target else 0, layers))
-        with torch.cuda.device(self.device):
-            return {k: v.clone() for k, v in self._tensors(layers).items()}
-
-    def grads(self) -> dict:
-        """Gradients of the last update under the parameters' key names (weight_norm: dg), as device copies."""
-        layers = (L.QcDqnLayer * 6)()
-        self._check(L.lib().qc_learner_grads(self._h, layers))
-        with torch.cuda.device(self.device):
-            return {k: v.clone() for k, v in self._tensors(layers).items()}
-
-    def apply(self, grads: Mapping[str, torch.Tensor]):
-        """One LaProp step on injected gradients (tests)."""
-        layers, keep = self._layer_array(grads)
-        with torch.cuda.device(self.device):
-            self._bind_stream()
-            self._check(L.lib().qc_learner_apply(self._h, layers))
-        self._keep = keep
-
-    def set_lr(self, lr: float):
-        self._check(L.lib().qc_learner_set_lr(self._h, float(lr)))
-
-    def update(self, transitions: torch.Tensor, is_weights: torch.Tensor, noise: Optional[torch.Tensor] = None,
-               counter: Optional[int] = None) -> torch.Tensor:
-        """One update on transitions [batch_size, 2 data_length + 2] and IS weights [batch_size]. noise: optional
-        [32, noise_len], already f-transformed, the actor's layout per chunk; else Philox (seed, chunk, counter).
-        Returns unweighted_loss [batch_size] (device); the scalar loss stays in `last_loss` (device).
-        Asynchronous: an action outside [0, n_actions) is clamped and raised by the next `stats()`."""
-        if transitions.dim() != 2 or tuple(transitions.shape) != (self.batch_size, self.row_len):
-            raise ValueError(f"transitions must be [{self.batch_size}, {self.row_len}]")
-        if is_weights.numel() != self.batch_size:
-            raise ValueError(f"is_weights must be [{self.batch_size}]")
-        tr = transitions.to(device=self.device, dtype=torch.float32).contiguous()
-        w = is_weights.to(device=self.device, dtype=torch.float32).contiguous()
-        nz = None
-        if noise is not None:
-            if tuple(noise.shape) != (32, self.noise_len):
-                raise ValueError(f"noise must be [32, {self.noise_len}]")
-            nz = noise.to(device=self.device, dtype=torch.float32).contiguous()
-        if counter is None:
-            counter = self.counter
-            self.counter += 1
-        ul = torch.empty(self.batch_size, dtype=torch.float32, device=self.device)
-        vp = ctypes.c_void_p
-        with torch.cuda.device(self.device):
-            self._bind_stream()
-            self._check(L.lib().qc_learner_update(
-                self._h, vp(tr.data_ptr()), vp(w.data_ptr()), vp(nz.data_ptr()) if nz is not None else None,
-                int(counter), vp(ul.data_ptr()), vp(self.last_loss.data_ptr())))
-        return ul
-
-    def step(self, memory, counter: Optional[int] = None):
-        """TrainDQN.__call__: obtain_sample -> update -> memory.batch_update(tree_idx, unweighted_loss). None
-        while len(memory) < batch_size (RL.py:161)."""
-        smp = memory.obtain_sample(self.batch_size)
-        if smp is None:
-            return None
-        tree_idx, is_weights, transitions = smp
-        ul = self.update(transitions, is_weights, counter=counter)
-        memory.batch_update(tree_idx, ul)
-        return ul
-
     def push(self, actor):
         """Load the online fc1, fc2, fc31, fc41 into a DQNActor, device to device (no host copy). The actor's
         net must be the learner's: the load reads the tensors at the actor's own sizes."""
@@ -210,17 +256,7 @@ class DQNLearner(L.DeviceHandle):
             raise ValueError(f"push: the actor's net (hidden2 {actor.hidden2}, data_length {actor.data_length}, "
                              f"n_actions {actor.n_actions}) is not the learner's (hidden2 {self.hidden2}, "
                              f"data_length {self.data_length}, n_actions {self.n_actions})")
-        layers = (L.QcDqnLayer * 6)()
-        self._check(L.lib().qc_learner_layers(self._h, 0, layers))
-        with torch.cuda.device(self.device):
-            actor._bind_stream()
-            L.check_actor(L.lib().qc_actor_load(actor._h, layers), actor._h)
-
-    def stats(self) -> dict:
-        """Synchronises. Raises QCartError if an update since the last call saw an out-of-range action."""
-        s = L.QcLearnerStats()
-        self._check(L.lib().qc_learner_stats(self._h, ctypes.byref(s)))
-        return {k: getattr(s, k) for k, _ in L.QcLearnerStats._fields_}
+        self._push(actor, L.lib().qc_actor_load, L.check_actor)
 
 
 M_LEARNER_LAYERS = ("conv1", "conv2", "conv3", "fc1", "fc21", "fc31", "fc22", "fc32")
@@ -232,7 +268,7 @@ def measurement_row_len(read_length: int, read_step_length: int) -> int:
     return read_length + read_step_length + read_length // read_step_length + 3
 
 
-class MeasurementLearner(L.DeviceHandle):
+class MeasurementLearner(_Learner):
     """TrainDQN for DQN_measurement (the 'measurements' input, RL.py:29-78 and :159-232) with centred LaProp: one
     update per call on `batch_size` rows of MeasurementRecord (csrc/qcart_mlearner.hip, `qc_mlearner_update`),
     without leaving the device:
@@ -256,30 +292,19 @@ class MeasurementLearner(L.DeviceHandle):
     is refused. batch_size: a multiple of 128 in [128, 1024]."""
 
     _prefix = "qc_mlearner"
+    _n_layers = 8
+    _max_batch = 1024
 
     def __init__(self, params: Mapping[str, torch.Tensor], read_length: int, read_step_length: int,
                  batch_size: int = 512, gamma: float = 0.998, lr: float = 4e-4, alive_reward: float = 10.,
                  failing_reward: float = -1., backup_period: int = 300, target: str = "alive",
                  betas=(0.9, 0.9995), device: int | str | torch.device = 0, seed: int = 0):
-        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("MeasurementLearner runs on a HIP device only (no CPU fallback)")
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        if batch_size % 128 != 0 or not 128 <= batch_size <= 1024:
-            raise ValueError("batch_size must be a multiple of 128 in [128, 1024] (FactorizedNoisy's 32-chunk "
-                             "noise branch; the per-row branch of other sizes is not implemented)")
+        self._resolve(device, batch_size)
         if "conv1.weight" not in params or "fc31.u_w" not in params:
             raise ValueError("params must be a DQN_measurement state_dict (conv1.weight, ..., fc31.u_w)")
         if read_step_length < 1 or read_length % read_step_length != 0:
             raise ValueError(f"read_length {read_length} must be a multiple of read_step_length {read_step_length}")
-        if target not in L.TD_TARGETS:
-            raise ValueError(f"target must be one of {sorted(L.TD_TARGETS)}, not {target!r}")
-        self.target = target
-        self.betas = (float(betas[0]), float(betas[1]))
-        for name, b in zip(("beta1", "beta2"), self.betas):
-            if not 0. < b < 1.:
-                raise ValueError(f"{name} (betas) must be in (0, 1), not {b}")
+        self._schedule(target, betas)
         self.read_length, self.read_step_length = int(read_length), int(read_step_length)
         self.n_actions = int(params["fc31.u_w"].shape[0])
         self.batch_size = int(batch_size)
@@ -288,29 +313,15 @@ class MeasurementLearner(L.DeviceHandle):
         self.row_len = measurement_row_len(self.read_length, self.read_step_length)
         p = L.QcMlearnerParams()
         p.read_length, p.read_step_length = self.read_length, self.read_step_length
-        p.n_actions, p.batch_size = self.n_actions, self.batch_size
-        p.backup_period, p.target_mode = int(backup_period), L.TD_TARGETS[target]
-        p.gamma, p.lr = float(gamma), float(lr)
-        p.alive_reward, p.failing_reward, p.seed = float(alive_reward), float(failing_reward), int(seed)
-        p.beta1, p.beta2 = self.betas
         p.conv_weight_norm = 1 if self.conv_weight_norm else 0
-        h = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            torch.cuda.init()
-            self._check(L.lib().qc_mlearner_create(ctypes.byref(p), self.device.index, ctypes.byref(h)))
-        self._h = h
-        self.noise_len = int(L.lib().qc_mlearner_noise_len(h))
-        self.counter = 0
-        self.last_loss = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self._keep = []
-        self.load_state_dict(params)
+        self._create(p, params, gamma, lr, alive_reward, failing_reward, backup_period, seed)
 
     def _shapes(self):
         return [(o, i, k) for i, o, k, _ in M_CONV] + [(256, self.flat_len), (256, 256), (self.n_actions, 256),
                                                        (128, 256), (1, 128)]
 
     def _layer_array(self, params: Mapping[str, torch.Tensor]):
-        layers = (L.QcDqnLayer * 8)()
+        layers = self._layers()
         keep = []
         for i, (name, shape) in enumerate(zip(M_LEARNER_LAYERS, self._shapes())):
             if _M_KIND[i] in ("conv", "plain"):
@@ -333,16 +344,6 @@ class MeasurementLearner(L.DeviceHandle):
             L.fill_layer(layers[i], ts)
         return layers, keep
 
-    def load_state_dict(self, params: Mapping[str, torch.Tensor]):
-        """Load the eight layers from a DQN_measurement state_dict (the reference's, or
-        actor.random_dqn_measurement's) of the handle's kind of convolutions; resets the optimizer state and the
-        target schedule."""
-        layers, keep = self._layer_array(params)
-        with torch.cuda.device(self.device):
-            self._bind_stream()
-            self._check(L.lib().qc_mlearner_load(self._h, layers))
-        self._keep = keep   # the copies read them on the current stream
-
     def _tensors(self, layers) -> dict:
         out = {}
         for i, (name, shape) in enumerate(zip(M_LEARNER_LAYERS, self._shapes())):
@@ -364,36 +365,6 @@ class MeasurementLearner(L.DeviceHandle):
                     out[f"{name}.weight_norm"] = _view(ly.weight_norm, 1, torch.float32, self.device).view(())
         return out
 
-    def state_dict(self, target: bool = False) -> dict:
-        """The online (or target) parameters under the reference's key names, as device copies."""
-        layers = (L.QcDqnLayer * 8)()
-        self._check(L.lib().qc_mlearner_layers(self._h, 1 if target else 0, layers))
-        with torch.cuda.device(self.device):
-            return {k: v.clone() for k, v in self._tensors(layers).items()}
-
-    def grads(self) -> dict:
-        """Gradients of the last update under the parameters' key names (weight_norm: dg), as device copies."""
-        layers = (L.QcDqnLayer * 8)()
-        self._check(L.lib().qc_mlearner_grads(self._h, layers))
-        with torch.cuda.device(self.device):
-            return {k: v.clone() for k, v in self._tensors(layers).items()}
-
-    def apply(self, grads: Mapping[str, torch.Tensor]):
-        """One LaProp step on injected gradients (tests)."""
-        layers, keep = self._layer_array(grads)
-        with torch.cuda.device(self.device):
-            self._bind_stream()
-            self._check(L.lib().qc_mlearner_apply(self._h, layers))
-        self._keep = keep
-
-    def set_lr(self, lr: float):
-        self._check(L.lib().qc_mlearner_set_lr(self._h, float(lr)))
-
-    def _rows(self, transitions: torch.Tensor) -> torch.Tensor:
-        if transitions.dim() != 2 or tuple(transitions.shape) != (self.batch_size, self.row_len):
-            raise ValueError(f"transitions must be [{self.batch_size}, {self.row_len}]")
-        return transitions.to(device=self.device, dtype=torch.float32).contiguous()
-
     def states(self, transitions: torch.Tensor):
         """(next, prev) [batch_size, 2, read_length]: the states the update assembles from the rows (tests)."""
         tr = self._rows(transitions)
@@ -405,55 +376,9 @@ class MeasurementLearner(L.DeviceHandle):
             self._check(L.lib().qc_mlearner_states(self._h, vp(tr.data_ptr()), vp(nxt.data_ptr()), vp(prv.data_ptr())))
         return nxt, prv
 
-    def update(self, transitions: torch.Tensor, is_weights: torch.Tensor, noise: Optional[torch.Tensor] = None,
-               counter: Optional[int] = None) -> torch.Tensor:
-        """One update on rows [batch_size, row_len] and IS weights [batch_size]; noise, counter, the return
-        value and the out-of-range-action report as DQNLearner.update."""
-        tr = self._rows(transitions)
-        if is_weights.numel() != self.batch_size:
-            raise ValueError(f"is_weights must be [{self.batch_size}]")
-        w = is_weights.to(device=self.device, dtype=torch.float32).contiguous()
-        nz = None
-        if noise is not None:
-            if tuple(noise.shape) != (32, self.noise_len):
-                raise ValueError(f"noise must be [32, {self.noise_len}]")
-            nz = noise.to(device=self.device, dtype=torch.float32).contiguous()
-        if counter is None:
-            counter = self.counter
-            self.counter += 1
-        ul = torch.empty(self.batch_size, dtype=torch.float32, device=self.device)
-        vp = ctypes.c_void_p
-        with torch.cuda.device(self.device):
-            self._bind_stream()
-            self._check(L.lib().qc_mlearner_update(
-                self._h, vp(tr.data_ptr()), vp(w.data_ptr()), vp(nz.data_ptr()) if nz is not None else None,
-                int(counter), vp(ul.data_ptr()), vp(self.last_loss.data_ptr())))
-        return ul
-
-    def step(self, memory, counter: Optional[int] = None):
-        """TrainDQN.__call__: obtain_sample -> update -> memory.batch_update(tree_idx, unweighted_loss). None
-        while len(memory) < batch_size (RL.py:161)."""
-        smp = memory.obtain_sample(self.batch_size)
-        if smp is None:
-            return None
-        tree_idx, is_weights, transitions = smp
-        ul = self.update(transitions, is_weights, counter=counter)
-        memory.batch_update(tree_idx, ul)
-        return ul
-
     def push(self, mactor):
         """Load the online conv1..3, fc1, fc21, fc31 into a MeasurementActor, device to device."""
         if (mactor.read_length, mactor.n_actions) != (self.read_length, self.n_actions):
             raise ValueError(f"push: the actor's net (read_length {mactor.read_length}, n_actions {mactor.n_actions}) "
                              f"is not the learner's (read_length {self.read_length}, n_actions {self.n_actions})")
-        layers = (L.QcDqnLayer * 8)()
-        self._check(L.lib().qc_mlearner_layers(self._h, 0, layers))
-        with torch.cuda.device(self.device):
-            mactor._bind_stream()
-            L.check_mactor(L.lib().qc_mactor_load(mactor._h, layers), mactor._h)
-
-    def stats(self) -> dict:
-        """Synchronises. Raises QCartError if an update since the last call saw an out-of-range action."""
-        s = L.QcLearnerStats()
-        self._check(L.lib().qc_mlearner_stats(self._h, ctypes.byref(s)))
-        return {k: getattr(s, k) for k, _ in L.QcLearnerStats._fields_}
+        self._push(mactor, L.lib().qc_mactor_load, L.check_mactor)
