@@ -91,9 +91,9 @@ class Grid:
 
 
 def grid_force(grid: Grid, state, strategy: str, con_parameter: float, lambda_: float, mass: float,
-               n_con: int):
-    """controllers.py:7-29 with control_time = 1 / controls_per_unit_time; returns F (before / pi)."""
-    T = 1. / n_con
+               n_con: int, control_time: float | None = None):
+    """controllers.py:7-29 with control_time = 1 / controls_per_unit_time unless given; returns F (before / pi)."""
+    T = 1. / n_con if control_time is None else control_time
     xe, pe, x2, x3, xpx = grid.expectations(state)
     if strategy == "damping":
         pp = pe - 4. * lambda_ * x3 * T - T ** 2 * 2. * lambda_ * 3. * xpx / mass
@@ -109,7 +109,7 @@ def grid_force(grid: Grid, state, strategy: str, con_parameter: float, lambda_: 
 
 
 def grid_control(grid: Grid, state, strategy: str, con_parameter: float, lambda_: float, mass: float,
-                 n_con: int, f_max: float):
+                 n_con: int, f_max: float, control_time: float | None = None):
     """analytic_controls (QO/main_parallel.py:165-181): (action, force)."""
-    F = grid_force(grid, state, strategy, con_parameter, lambda_, mass, n_con)
+    F = grid_force(grid, state, strategy, con_parameter, lambda_, mass, n_con, control_time)
     return _round_force(F / pi, f_max)
