@@ -41,7 +41,7 @@ EXPORTS = (
     "qc_replay_buffers", "qc_set_seed_mt19937_envs", "qc_mt19937_normals",
     "qc_server_create", "qc_server_run", "qc_server_stop", "qc_server_stats", "qc_server_timing", "qc_server_resident",
     "qc_server_last_error",
-    "qc_server_destroy", "qc_env_tail",
+    "qc_server_destroy", "qc_env_tail", "qc_env_warmup_draw",
     "qc_learner_create", "qc_learner_destroy", "qc_learner_last_error", "qc_learner_set_stream",
     "qc_learner_noise_len", "qc_learner_load", "qc_learner_layers", "qc_learner_update", "qc_learner_set_lr",
     "qc_learner_stats", "qc_learner_grads", "qc_learner_apply",
@@ -105,6 +105,18 @@ class QcEnvTailArgs(ctypes.Structure):
         ("t_trunc", ctypes.c_double),
         ("reward_multiply", ctypes.c_double),
         ("rec_mode", ctypes.c_void_p),
+        # the rolling warm-up of the quartic cooling driver (kind == QC_QO); zero / NULL otherwise
+        ("warm_left", ctypes.c_void_p),
+        ("warm_fail", ctypes.c_void_p),
+        ("draws", ctypes.c_void_p),
+        ("k", ctypes.c_void_p),
+        ("budget", ctypes.c_void_p),
+        ("init_energy_cutoff", ctypes.c_double),
+        ("init_lo", ctypes.c_double),
+        ("init_hi", ctypes.c_double),
+        ("seed", ctypes.c_uint64),
+        ("env_offset", ctypes.c_int64),
+        ("reset_out", ctypes.c_void_p),
     ]
 
 
@@ -269,6 +281,7 @@ def lib() -> ctypes.CDLL:
     L.qc_set_seed_mt19937_envs.argtypes = [vp, vp, vp]
     L.qc_mt19937_normals.argtypes = [vp, ctypes.c_int32, vp, vp, vp, vp]
     L.qc_env_tail.argtypes = [vp, P(QcEnvTailArgs)]
+    L.qc_env_warmup_draw.argtypes = [vp, P(QcEnvTailArgs), vp]
     L.qc_server_create.argtypes = [P(QcParams), ctypes.c_int, i32, ctypes.c_char_p, d, P(vp)]
     L.qc_server_run.argtypes = [vp, d]
     L.qc_server_stop.argtypes = [vp]

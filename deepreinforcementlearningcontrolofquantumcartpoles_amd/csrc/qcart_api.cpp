@@ -978,21 +978,8 @@ int qc_group_layout(qc_handle* h, int32_t* order, int64_t order_len, int32_t* mi
     return h->d_order_mixed ? (int)h->acts.size() : 0;
 }
 
-int qc_env_tail(qc_handle* h, const qc_env_tail_args* in) {
-    if (!h || !in) return QC_EINVAL;
-    const qc_env_tail_args& x = *in;
-    if (x.B != h->p.batch) return fail(h, QC_EINVAL, "env tail: B must be the handle's batch");
-    if (x.kind == QC_QO)
-        return fail(h, QC_EINVAL, "env tail: QO's reset (a free evolution of U[15, 20] time units, redrawn until "
-                                  "accepted) is no one-interval reset");
-    if (x.kind != QC_IHO && x.kind != QC_IQO && x.kind != QC_HO) return fail(h, QC_EINVAL, "env tail: unknown kind");
-    if (x.kind == QC_IQO && !x.term_step) return fail(h, QC_EINVAL, "env tail: IQO needs term_step");
-    if (x.kind == QC_HO && x.B > 0 && !x.quantity) return fail(h, QC_EINVAL, "env tail: HO needs quantity");
-    const bool need_obs = x.kind == QC_IHO || x.obs32;   // IHO decides by <x>; obs32 is converted from obs
-    if (x.B > 0 && (!x.fail_step || (need_obs && !x.obs) || !x.pending || !x.t || !x.steps || !x.episode_return ||
-                    !x.reward || !x.done || !x.valid || !x.fin || !x.fin_n || x.fin_cap < 1 || x.n_obs < 1 ||
-                    x.interval < 1))
-        return fail(h, QC_EINVAL, "env tail: missing buffer or bad size");
+// qc_env_tail_args -> the kernels' argument block (the two structs list the same fields)
+static EnvTailArgs env_tail_kargs(const qc_env_tail_args& x) {
     EnvTailArgs a;
     std::memset(&a, 0, sizeof(a));
     a.B = x.B;
@@ -1022,8 +1009,59 @@ int qc_env_tail(qc_handle* h, const qc_env_tail_args* in) {
     a.t_trunc = x.t_trunc;
     a.reward_multiply = x.reward_multiply;
     a.rec_mode = x.rec_mode;
+    a.warm_left = x.warm_left;
+    a.warm_fail = x.warm_fail;
+    a.draws = x.draws;
+    a.k = x.k;
+    a.budget = x.budget;
+    a.init_energy_cutoff = x.init_energy_cutoff;
+    a.init_lo = x.init_lo;
+    a.init_hi = x.init_hi;
+    a.seed = x.seed;
+    a.env_offset = x.env_offset;
+    a.reset_out = x.reset_out;
+    return a;
+}
+
+static bool warmup_state_missing(const qc_env_tail_args& x) {
+    return !x.warm_left || !x.warm_fail || !x.draws || !x.k || !x.budget || !x.pending;
+}
+
+int qc_env_tail(qc_handle* h, const qc_env_tail_args* in) {
+    if (!h || !in) return QC_EINVAL;
+    const qc_env_tail_args& x = *in;
+    if (x.B != h->p.batch) return fail(h, QC_EINVAL, "env tail: B must be the handle's batch");
+    if (x.kind == QC_QO && (warmup_state_missing(x) || !x.reset_out))
+        return fail(h, QC_EINVAL, "env tail: QO's reset (a free evolution of U[15, 20] time units, redrawn until "
+                                  "accepted) is no one-interval reset: it needs the warm-up state (warm_left, "
+                                  "warm_fail, draws, k, budget, reset_out)");
+    if (x.kind != QC_IHO && x.kind != QC_IQO && x.kind != QC_HO && x.kind != QC_QO)
+        return fail(h, QC_EINVAL, "env tail: unknown kind");
+    if (x.kind == QC_IQO && !x.term_step) return fail(h, QC_EINVAL, "env tail: IQO needs term_step");
+    if (x.kind == QC_HO && x.B > 0 && !x.quantity) return fail(h, QC_EINVAL, "env tail: HO needs quantity");
+    if (x.kind == QC_QO && (!x.quantity || !(x.dt > 0) || !(x.init_lo >= 0) || !(x.init_hi >= x.init_lo)))
+        return fail(h, QC_EINVAL, "env tail: QO needs quantity (the energy), dt > 0 and 0 <= init_lo <= init_hi");
+    const bool need_obs = x.kind == QC_IHO || x.obs32;   // IHO decides by <x>; obs32 is converted from obs
+    if (x.B > 0 && (!x.fail_step || (need_obs && !x.obs) || !x.pending || !x.t || !x.steps || !x.episode_return ||
+                    !x.reward || !x.done || !x.valid || !x.fin || !x.fin_n || x.fin_cap < 1 || x.n_obs < 1 ||
+                    x.interval < 1))
+        return fail(h, QC_EINVAL, "env tail: missing buffer or bad size");
+    const EnvTailArgs a = env_tail_kargs(x);
     DeviceGuard g(h->device);
     return launch_env_tail(a, h->stream) ? fail(h, QC_EHIP, "env tail kernel launch failed") : QC_OK;
+}
+
+int qc_env_warmup_draw(qc_handle* h, const qc_env_tail_args* in, const uint8_t* mask) {
+    if (!h || !in) return QC_EINVAL;
+    const qc_env_tail_args& x = *in;
+    if (x.B != h->p.batch) return fail(h, QC_EINVAL, "env warm-up draw: B must be the handle's batch");
+    if (x.kind != QC_QO) return fail(h, QC_EINVAL, "env warm-up draw: the quartic cooling driver (QC_QO) only");
+    if (warmup_state_missing(x) || !x.t || !x.steps || !x.episode_return || x.interval < 1 || !(x.dt > 0) ||
+        !(x.init_lo >= 0) || !(x.init_hi >= x.init_lo))
+        return fail(h, QC_EINVAL, "env warm-up draw: missing buffer, interval < 1, dt <= 0 or not 0 <= init_lo <= init_hi");
+    const EnvTailArgs a = env_tail_kargs(x);
+    DeviceGuard g(h->device);
+    return launch_warmup_draw(a, mask, h->stream) ? fail(h, QC_EHIP, "env warm-up draw kernel launch failed") : QC_OK;
 }
 
 int qc_take_errors(qc_handle* h) {

@@ -201,8 +201,19 @@ struct EnvTailArgs {
     const double* quantity;   // kind == QC_HO: the phonon number
     double cutoff, t_trunc, reward_multiply;
     uint8_t* rec_mode;        // optional
+    // kind == QC_QO: the rolling warm-up's per-env state, its draw parameters and the went-live flag
+    int32_t* warm_left;
+    uint8_t* warm_fail;
+    int64_t* draws;
+    double* k;
+    int32_t* budget;
+    double init_energy_cutoff, init_lo, init_hi;
+    uint64_t seed;
+    int64_t env_offset;
+    uint8_t* reset_out;
 };
 int launch_env_tail(const EnvTailArgs& a, void* stream);
+int launch_warmup_draw(const EnvTailArgs& a, const uint8_t* mask, void* stream);   // qc_env_warmup_draw
 
 // reference noise stream (qcart_noise.hip): per-env MT19937 state [B][kMtWords] uint32 (624 words,
 // the read index, one pad word)

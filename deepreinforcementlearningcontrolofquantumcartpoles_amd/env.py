@@ -26,7 +26,7 @@ the observation is get_data_wavefunction(state) * input_scaling: float32 hstack(
 experience rows [B][row_len] come from the same kernel (info['rows']).
 
 Auto-reset modes (reset="deferred": HO, IHO and IQO with every input they have; QO's reset is hundreds of control
-intervals drawn from a host generator, no one-interval reset, and stays with "immediate"):
+intervals, no one-interval reset: it has "immediate" and "warmup"):
   * reset="immediate" (default): a finished env is reset and runs its zero-force first interval inside the same
     step() call, so the returned obs of a done env is already the next episode's first observation (the terminal
     one is info['terminal_obs']) — the reference actor's own interleaving; one more (partial) step launch and a few
@@ -44,6 +44,17 @@ intervals drawn from a host generator, no one-interval reset, and stays with "im
     env in its reset interval, append otherwise); obs is the record, which holds a done env's terminal record
     until the next call restarts it, and info['rows'] / info['valid'] are the immediate mode's
     (tests/test_gpu_env_deferred_inputs.py: per-env rows and episodes bitwise equal).
+  * reset="warmup" (QO only, 'xp' and 'wavefunction'): a finished env, or one whose warm-up was rejected, draws a
+    new packet (k, evolution time from init_time) on the device and runs its free evolution inside the following
+    calls' step launches, control_interval physics steps per call (the last call fewer: per-env step budgets), while
+    the other envs are controlled. Every call is one masked packet reset, one step, one energy and one tail kernel
+    (qc_env_tail, kind QC_QO) and never synchronises with the host. A warming env's action is ignored
+    (info['warming']), it returns reward 0, done False and no valid transition; in the call that ends an accepted
+    warm-up info['reset'] is set and the returned observation is the episode's first (QO decides at i = 0). A
+    transition is valid exactly when the env was live on entry and is not done. reset() only starts the warm-ups
+    and returns the observation buffer as it is. The draws come from the env's own Philox stream, not
+    from the immediate mode's torch generator, and the warm-up runs in control intervals instead of 1440-step
+    launches: the scheme is the immediate mode's, the trajectories are not bitwise its.
 """
 from __future__ import annotations
 
@@ -52,6 +63,7 @@ from typing import Optional
 
 import torch
 
+from . import _lib as L
 from . import config as cfg
 from .core import Stepper
 from .measurements import MeasurementRecord
@@ -63,7 +75,7 @@ class BatchedEnv:
                  reward_multiply: float = 1.0, t_max: float = 100.0, phonon_cutoff: float = 20.0,
                  energy_cutoff: float = 12.0, init_energy_cutoff: float = 7.5, auto_reset: bool = True,
                  reset_kind: str = "reference", input: str = "xp", read_length: Optional[int] = None,
-                 reset: str = "immediate"):
+                 reset: str = "immediate", init_time: tuple = (15.0, 20.0)):
         self.ph = physics
         self.B = int(batch)
         self.st = Stepper(physics, self.B, device, seed=seed, env_offset=env_offset)
@@ -78,6 +90,10 @@ class BatchedEnv:
         self.phonon_cutoff = phonon_cutoff
         self.energy_cutoff = energy_cutoff
         self.init_energy_cutoff = init_energy_cutoff
+        # QO: the free evolution of a reset lasts U[init_time] time units (QO/main_parallel.py:186)
+        self.init_time = (float(init_time[0]), float(init_time[1]))
+        if not 0.0 <= self.init_time[0] <= self.init_time[1] < float("inf"):
+            raise ValueError("init_time must be (lo, hi) with 0 <= lo <= hi")
         self.auto_reset = auto_reset
         self.reset_kind = reset_kind
         self.cartpole = physics.family in (cfg.IHO, cfg.IQO)
@@ -89,12 +105,17 @@ class BatchedEnv:
         if input == "measurements" and not physics.fock:
             raise ValueError("the 'measurements' input exists for the Fock families (HO, IHO) only")
         self.input = input
-        if reset not in ("immediate", "deferred"):
-            raise ValueError("reset must be 'immediate' or 'deferred'")
+        if reset not in ("immediate", "deferred", "warmup"):
+            raise ValueError("reset must be 'immediate', 'deferred' or 'warmup'")
+        if reset == "warmup" and physics.family != cfg.QO:
+            raise ValueError("reset='warmup' is the quartic cooling driver's (QO) rolling reset; HO, IHO and IQO have "
+                             "a one-interval reset: use reset='deferred'")
+        if reset == "warmup" and not auto_reset:
+            raise ValueError("reset='warmup' is an auto-reset mode: it needs auto_reset")
         if reset == "deferred" and physics.family == cfg.QO:
             raise ValueError("reset='deferred' needs a one-interval reset: QO's is a random packet evolved freely for "
                              "U[15, 20] time units and redrawn until accepted (QO/main_parallel.py:177-198), hundreds "
-                             "of control intervals drawn from a host generator; use reset='immediate'")
+                             "of control intervals; use reset='warmup' (or 'immediate')")
         if reset == "deferred" and not auto_reset:
             raise ValueError("reset='deferred' is an auto-reset mode (HO, IHO, IQO): it needs auto_reset")
         self.reset_mode = reset
@@ -121,6 +142,15 @@ class BatchedEnv:
         self._fin_n = torch.zeros((), dtype=torch.int64, device=self.dev)
         self._fin_read = 0
         self._fin_host: list = []
+        if reset == "warmup":
+            # per-env warm-up state, advanced by qc_env_tail (kind QC_QO) and started by qc_env_warmup_draw
+            self._seed, self._env_offset = int(seed), int(env_offset)
+            self._warm_left = z(torch.int32)      # physics steps of free evolution still to run; warming iff > 0
+            self._warm_fail = z(torch.uint8)      # a Fail was seen during this warm-up
+            self._draws = z(torch.int64)          # reset draws consumed
+            self._k = z(torch.float64)            # the packet's wavenumber
+            self._budget = torch.full((self.B,), self.ci, dtype=torch.int32, device=self.dev)   # next call's env_steps
+            self._mean0, self._std1 = z(torch.float64), torch.ones(self.B, dtype=torch.float64, device=self.dev)
 
     @property
     def finished_returns(self) -> list:
@@ -184,7 +214,8 @@ class BatchedEnv:
             mu = torch.zeros(self.B, dtype=torch.float64, device=self.dev)
             sg = torch.ones(self.B, dtype=torch.float64, device=self.dev)
             self.st.reset(self.psi, 2, mask=todo.to(torch.uint8), k=k, mean=mu, std=sg)
-            init_t = torch.rand(self.B, generator=self.gen, device=self.dev, dtype=torch.float64) * 5.0 + 15.0
+            lo, hi = self.init_time
+            init_t = torch.rand(self.B, generator=self.gen, device=self.dev, dtype=torch.float64) * (hi - lo) + lo
             budget = torch.where(todo, torch.ceil(init_t / dt).to(torch.int32), torch.zeros_like(init_t, dtype=torch.int32))
             failed = torch.zeros(self.B, dtype=torch.bool, device=self.dev)
             chunk = 1440
@@ -201,6 +232,16 @@ class BatchedEnv:
         if mask is None:
             mask = torch.ones(self.B, dtype=torch.bool, device=self.dev)
         mask = mask.to(device=self.dev, dtype=torch.bool)
+        if self.reset_mode == "warmup":
+            # the masked envs start a warm-up (a pending packet of an earlier draw is replaced by the new one); the
+            # first real observation of an env is the one flagged by info['reset']
+            a = self._warmup_args()
+            self.st._bind_stream()
+            m8 = mask.to(torch.uint8).contiguous()
+            L.check(L.lib().qc_env_warmup_draw(self.st._h, ctypes.byref(a), ctypes.c_void_p(m8.data_ptr())),
+                    self.st._h)
+            self.last_action = torch.where(mask, torch.full_like(self.last_action, self.half), self.last_action)
+            return self.obs
         self._pending.masked_fill_(mask, 0)   # (reset='deferred': a pending reset is done here instead)
         self._reset_states(mask)
         self.t = torch.where(mask, torch.zeros_like(self.t), self.t)
@@ -246,7 +287,6 @@ class BatchedEnv:
     def _step_deferred(self, actions: torch.Tensor):
         """reset='deferred': the envs finished in the previous call take their reset interval now (reset kernel +
         the zero force in the same step launch), then qc_env_tail does the bookkeeping on the device."""
-        from . import _lib as L
         fam = self.ph.family
         pend = self._pending
         reset_now = pend.clone().view(torch.bool)
@@ -297,6 +337,52 @@ class BatchedEnv:
                      "numerical_failure": done_b & (out["fail_step"] > 0)})
         return obs, reward, done_b, info
 
+    def _warmup_args(self, **kw):
+        """qc_env_tail_args of the warm-up mode: the per-env state and the draw parameters (kw: the per-call fields)."""
+        p = lambda t: t.data_ptr()   # noqa: E731
+        return L.QcEnvTailArgs(
+            B=self.B, kind=cfg.QO, n_obs=self.st.n_obs, interval=self.ci, dt=self.ph.dt,
+            input_scaling=self.input_scaling, pending=p(self._pending), t=p(self.t), steps=p(self.steps),
+            episode_return=p(self.episode_return), fin=p(self._fin), fin_cap=self._fin_cap, fin_n=p(self._fin_n),
+            cutoff=self.energy_cutoff, t_trunc=self.t_max - 0.01 * self.ph.dt, reward_multiply=self.reward_multiply,
+            warm_left=p(self._warm_left), warm_fail=p(self._warm_fail), draws=p(self._draws), k=p(self._k),
+            budget=p(self._budget), init_energy_cutoff=self.init_energy_cutoff, init_lo=self.init_time[0],
+            init_hi=self.init_time[1], seed=self._seed, env_offset=self._env_offset, **kw)
+
+    def _step_warmup(self, actions: torch.Tensor):
+        """reset='warmup' (QO): the packets of the new draws, one step launch with per-env budgets (a warming env at
+        zero force), the energy, then qc_env_tail's QO branch: accounting, warm-up bookkeeping and redraws."""
+        warming = self._warm_left > 0
+        self.st.reset(self.psi, L.QC_RESET_GAUSSIAN, mask=self._pending, k=self._k, mean=self._mean0, std=self._std1)
+        acts = torch.where(warming, torch.full_like(actions, self.half), actions)
+        out = self.st.step(self.psi, acts, self.ci, env_steps=self._budget, want_fail=True, want_obs=True)
+        energy = self.st.energy(self.psi)
+        B = self.B
+        obs = torch.empty((B, self.st.n_obs), dtype=torch.float32, device=self.dev) if self.input == "xp" else None
+        reward = torch.empty(B, dtype=torch.float32, device=self.dev)
+        done = torch.empty(B, dtype=torch.uint8, device=self.dev)
+        valid = torch.empty(B, dtype=torch.uint8, device=self.dev)
+        went_live = torch.empty(B, dtype=torch.uint8, device=self.dev)
+        a = self._warmup_args(fail_step=out["fail_step"].data_ptr(), obs=out["obs"].data_ptr(),
+                              obs32=obs.data_ptr() if obs is not None else None, reward=reward.data_ptr(),
+                              done=done.data_ptr(), valid=valid.data_ptr(), quantity=energy.data_ptr(),
+                              reset_out=went_live.data_ptr())
+        self.st._bind_stream()
+        L.check(L.lib().qc_env_tail(self.st._h, ctypes.byref(a)), self.st._h)
+        if self.input == "wavefunction":
+            obs = self.st.wavefunction_obs(self.psi, self.input_scaling)
+        last_obs = self.obs
+        self.obs = obs
+        self.last_action = acts
+        self._calls += 1
+        if self._calls % 16 == 0:   # deferred action-range errors, at most 16 calls late (synchronises)
+            self.st.check()
+        done_b = done.view(torch.bool)
+        info = {"valid": valid.view(torch.bool), "reset": went_live.view(torch.bool), "warming": warming,
+                "t": self.t.clone(), "last_obs": last_obs, "fail_step": out["fail_step"],
+                "numerical_failure": done_b & (out["fail_step"] > 0)}
+        return obs, reward, done_b, info
+
     def step(self, actions: torch.Tensor):
         """Apply per-env actions for one control interval. Returns (obs, reward, done, info):
         reward is the reference's stored reward-row value, info['valid'] marks transitions the
@@ -304,6 +390,8 @@ class BatchedEnv:
         actions = actions.to(device=self.dev, dtype=torch.int32).contiguous()
         if self.reset_mode == "deferred":
             return self._step_deferred(actions)
+        if self.reset_mode == "warmup":
+            return self._step_warmup(actions)
         last_obs = self.obs
         fam = self.ph.family
         out = self.st.step(self.psi, actions, self.ci, want_fail=True, want_obs=True,

@@ -575,11 +575,36 @@ int qc_mlearner_states(qc_mlearner* l, const float* transitions, float* next_out
  * reward_multiply; valid = !done (the terminal transition of a cooling episode is not stored); return += reward
  * where valid, the product and the sum each rounded once. obs may be NULL for QC_HO when obs32 is NULL. The
  * fields after fin_n are read for QC_HO only, except rec_mode, which every kind writes when it is not NULL; a
- * struct that leaves them zero with kind QC_IHO or QC_IQO behaves as before they existed. QC_QO is refused: its
- * reset (a packet evolved freely for U[15, 20] time units and redrawn until accepted) is no one-interval reset. */
+ * struct that leaves them zero with kind QC_IHO or QC_IQO behaves as before they existed.
+ * kind == QC_QO (BatchedEnv reset="warmup") is the quartic cooling accounting (QO/main_parallel.py:169-232) with a
+ * rolling warm-up: QO's reset (QO:177-198: a packet of wavenumber k ~ U[-0.3, 0.3] evolved freely for U[init_lo,
+ * init_hi] time units and redrawn until energy < init_energy_cutoff with no Fail) is no one-interval reset, so it
+ * runs inside the step launches of the following calls, budget[e] <= interval physics steps per call (qc_step's
+ * env_steps), while the other envs are controlled. The fields after rec_mode carry it; a struct that leaves them
+ * zero is refused with kind QC_QO as before they existed. quantity[e] is qc_energy after the step. Per env:
+ *   - warm_left[e] > 0 on entry (warming; the caller stepped it budget[e] steps at zero force): left = warm_left -
+ *     budget, warm_fail |= fail_step > 0; reward 0, not done, not valid. left > 0: warm_left = left, budget =
+ *     min(left, interval). left == 0 and no Fail and quantity < init_energy_cutoff (strict: a NaN rejects): the
+ *     env goes live: warm_left = warm_fail = 0, t = 0, steps = 0, return = 0, budget = interval, reset_out = 1 —
+ *     this call's observation is the episode's first (QO decides at i = 0, QO:208, where the energy is not
+ *     checked against cutoff). Otherwise the env redraws.
+ *   - live: t += interval dt, steps += interval, done = Fail or !(quantity < cutoff) or t >= t_trunc; reward =
+ *     -quantity * reward_multiply; valid = !done; return += reward where valid, the product and the sum each
+ *     rounded once; budget = interval. A done env is appended to the ring (return, t) in env order and redraws;
+ *     its t and return keep the finished episode's values until it goes live again.
+ *   - redraw: n = draws[e], draws[e] = n + 1; (w0, w1, w2, w3) = Philox4x32-10 with key (seed_lo, seed_hi) at
+ *     counter (n_lo, n_hi, env_offset + e, 0x400); u_k = ((w0 << 32 | w1) >> 11) 2^-53, u_t likewise from (w2,
+ *     w3); k[e] = u_k 0.6 - 0.3; init_t = init_lo + u_t (init_hi - init_lo), each operation rounded once;
+ *     warm_left = ceil(init_t / dt) clamped to [1, 2^31 - 1]; warm_fail = 0; budget = min(warm_left, interval);
+ *     pending = 1: the caller writes the packet (qc_reset QC_RESET_GAUSSIAN, mask = pending, k_arr = k, mean 0,
+ *     std 1) before its next qc_step. pending (out) is 0 for every other env; reset_out is 0 unless the env went
+ *     live. rec_mode, when given, is written as for the other kinds.
+ * qc_env_warmup_draw starts the warm-up of the envs with mask[e] != 0 (mask NULL: all) by the same draw and zeroes
+ * their t, steps and return; it reads B, kind (QC_QO), interval, dt, pending, t, steps, episode_return and the
+ * fields after rec_mode except init_energy_cutoff and reset_out. */
 typedef struct qc_env_tail_args {
     int64_t B;
-    int32_t kind;             /* enum qc_family: QC_IHO or QC_IQO (cartpoles), QC_HO (cooling) */
+    int32_t kind;             /* enum qc_family: QC_IHO or QC_IQO (cartpoles), QC_HO or QC_QO (cooling) */
     int32_t n_obs, interval;  /* observables per env; physics steps per control interval */
     int32_t pad;
     double dt, xth, input_scaling, failing_reward;
@@ -602,8 +627,19 @@ typedef struct qc_env_tail_args {
     double t_trunc;           /* QC_HO: the episode is truncated when t >= t_trunc (t_max - 0.01 dt) */
     double reward_multiply;   /* QC_HO: reward = -quantity * reward_multiply */
     uint8_t* rec_mode;        /* [B] or NULL: qc_record's mode, 2 for an env pending on entry, else 1 */
+    int32_t* warm_left;       /* [B] QC_QO: physics steps of free evolution still to run; warming iff > 0 */
+    uint8_t* warm_fail;       /* [B] QC_QO: a Fail was seen during this warm-up */
+    int64_t* draws;           /* [B] QC_QO: reset draws the env has consumed */
+    double* k;                /* [B] QC_QO: the packet's wavenumber */
+    int32_t* budget;          /* [B] QC_QO: in: the steps of this call (qc_step's env_steps); out: the next call's */
+    double init_energy_cutoff;/* QC_QO: a warm-up is accepted when quantity < init_energy_cutoff and no Fail */
+    double init_lo, init_hi;  /* QC_QO: the free evolution lasts U[init_lo, init_hi) time units */
+    uint64_t seed;            /* QC_QO: Philox key of the draws */
+    int64_t env_offset;       /* QC_QO: global id of env 0 (Philox counter word 2 = env_offset + e) */
+    uint8_t* reset_out;       /* [B] QC_QO: 1 where the env went live in this call */
 } qc_env_tail_args;
 int qc_env_tail(qc_handle* h, const qc_env_tail_args* a);
+int qc_env_warmup_draw(qc_handle* h, const qc_env_tail_args* a, const uint8_t* mask);
 
 /* ---- step server: the reference's process model on one GPU ------------------------------------------------
  * The drivers run 30-40 actor processes, each with its own `simulation` module stepping ONE env per call

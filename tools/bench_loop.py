@@ -12,7 +12,10 @@ DQNActor at that length (122 / 302 / 322 / 1002 floats for --physics ho / qo / i
 fc2 512 wide for the quartic drivers) + the replay storing rows of 2 L + 2 floats (capacity --capacity rows,
 default 65 536: the drivers' 12.6 M rows of 2 006 floats would be 100 GB).
 Prints one JSON line: RL steps/s (decisions), env-steps/s and the actor's / replay's share of the loop.
-usage: python tools/bench_loop.py [--batch B] [--steps K] [--input xp|wavefunction|measurements] [--physics iho|iqo|ho|qo]"""
+With --physics qo --reset warmup the finished envs warm up inside the following calls (BatchedEnv reset='warmup');
+--t-max and --init-time set the episode truncation and the reset's free-evolution time.
+usage: python tools/bench_loop.py [--batch B] [--steps K] [--input xp|wavefunction|measurements] [--physics iho|iqo|ho|qo]
+       [--reset immediate|deferred|warmup] [--t-max T] [--init-time LO HI]"""
 import argparse
 import json
 import os
@@ -40,10 +43,16 @@ def main():
     ap.add_argument("--physics", choices=("iho", "iqo", "ho", "qo"), default="iho",
                     help="with --input wavefunction: the driver whose defaults the env runs (the other inputs run "
                          "the metric's IHO N = 512)")
-    ap.add_argument("--reset", choices=("immediate", "deferred"), default=None,
+    ap.add_argument("--reset", choices=("immediate", "deferred", "warmup"), default=None,
                     help="BatchedEnv auto-reset mode (deferred: finished envs reset in the next call's launch, no host "
                          "sync; every input of --physics ho / iho / iqo, not qo; the default for 'xp', immediate for "
-                         "the other inputs)")
+                         "the other inputs; warmup: --physics qo only, finished envs run their free evolution inside "
+                         "the following calls' launches)")
+    ap.add_argument("--t-max", type=float, default=None,
+                    help="episode truncation time (BatchedEnv t_max; the cooling drivers; default: the env's 100)")
+    ap.add_argument("--init-time", type=float, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="--physics qo: the reset's free evolution lasts U[LO, HI] time units (default: the driver's "
+                         "15 20)")
     ap.add_argument("--marker", action="store_true",
                     help="wrap the timed steps in a roctx range 'timed' (tools/loop_breakdown.py, rocprofv3 --marker-trace)")
     ap.add_argument("--learn", type=int, default=0,
@@ -60,7 +69,12 @@ def main():
     fam = {"iho": cfg.IHO, "iqo": cfg.IQO, "ho": cfg.HO, "qo": cfg.QO}[args.physics]
     ph = cfg.DEFAULTS[fam] if wave else cfg.DEFAULTS[cfg.IHO].with_(n_max=511)
     hidden2 = 512 if fam in (cfg.QO, cfg.IQO) else 256
-    env = BatchedEnv(ph, B, 0, seed=1, input=args.input, reset=args.reset)
+    env_kw = {}
+    if args.t_max is not None:
+        env_kw["t_max"] = args.t_max
+    if args.init_time is not None:
+        env_kw["init_time"] = tuple(args.init_time)
+    env = BatchedEnv(ph, B, 0, seed=1, input=args.input, reset=args.reset, **env_kw)
     L = int(env.obs.shape[1]) if wave else 5
     if meas:
         actor = MeasurementActor({k: v.cuda() for k, v in random_dqn_measurement(seed=1).items()}, max_batch=B, seed=2)
@@ -89,6 +103,7 @@ def main():
     marks = []                                          # (actor start, end, replay start, end) per timed step
     rows = torch.zeros((), dtype=torch.int64, device="cuda")
     n_done = torch.zeros((), dtype=torch.int64, device="cuda")
+    n_warming = torch.zeros((), dtype=torch.int64, device="cuda")
     # no host synchronisation inside the timed loop (device counters, events read afterwards): the loop's own
     # cost is what the GPU sees
     for it in range(args.warmup + args.steps):
@@ -99,6 +114,7 @@ def main():
             t0 = time.perf_counter()
             rows.zero_()
             n_done.zero_()
+            n_warming.zero_()
         m = [ev(), ev(), ev(), ev()]
         m[0].record()
         a = actor.act(obs, eps=DQNActor.eps_threshold(steps_done))
@@ -107,6 +123,8 @@ def main():
         obs, reward, done, info = env.step(a)
         rows += info["valid"].sum()
         n_done += done.sum()
+        if "warming" in info:
+            n_warming += info["warming"].sum()
         m[2].record()
         if meas:
             mem.store(info["rows"], info["valid"])
@@ -137,11 +155,17 @@ def main():
     net = "DQN_measurement" if meas else "direct_DQN"
     what = f"{args.physics.upper()} driver defaults" if wave else "IHO N=512"
     extra = {}
+    if args.reset == "warmup":   # share of the batch in its free evolution (not controlled) per call
+        extra["warming_fraction_per_control_step"] = int(n_warming) / (B * K)
+    if args.t_max is not None:
+        extra["t_max"] = args.t_max
+    if args.init_time is not None:
+        extra["init_time"] = list(args.init_time)
     if learner is not None:
         learn_ms = sum(a[3].elapsed_time(b[0]) for a, b in zip(marks[:-1], marks[1:]))
-        extra = {"learn_steps_per_control_step": args.learn,
-                 "learner_ms_per_control_step": learn_ms / max(K - 1, 1),
-                 "learner_nonfinite": learner.stats()["nonfinite"]}
+        extra.update({"learn_steps_per_control_step": args.learn,
+                      "learner_ms_per_control_step": learn_ms / max(K - 1, 1),
+                      "learner_nonfinite": learner.stats()["nonfinite"]})
     print(json.dumps({"metric": f"actor loop RL steps/s (BatchedEnv {what} input={args.input} reset={args.reset} + device {net} actor)",
                       "value": B * K / dt, "unit": "decisions/s", "env_steps_per_s": B * K * ph.control_interval / dt,
                       # physics env-steps actually taken: the immediate mode adds the reset intervals of the envs
