@@ -8,6 +8,7 @@ Modules:
   env         BatchedEnv: reset/step/observation semantics of the reference drivers, batched
   distributed env sharding over ranks + RCCL gather of episode returns
   learner     DQNLearner / MeasurementLearner: the reference's TrainDQN update on the device
+  checkpoint  save / load of the whole device loop; the resumed run is the uninterrupted one bit for bit
 """
 from .config import DEFAULTS, HO, IHO, IQO, QO, Physics  # noqa: F401
 

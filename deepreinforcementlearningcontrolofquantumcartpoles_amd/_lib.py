@@ -48,7 +48,8 @@ EXPORTS = (
     "qc_mlearner_create", "qc_mlearner_destroy", "qc_mlearner_last_error", "qc_mlearner_set_stream",
     "qc_mlearner_noise_len", "qc_mlearner_load", "qc_mlearner_layers", "qc_mlearner_update", "qc_mlearner_set_lr",
     "qc_mlearner_stats", "qc_mlearner_grads", "qc_mlearner_apply", "qc_mlearner_states",
-)
+) + tuple(f"qc_{kind}_state_{op}" for kind in ("actor", "mactor", "replay", "learner", "mlearner")
+          for op in ("bytes", "export", "import"))   # checkpoint: a handle's whole state as one host buffer
 
 
 class QcParams(ctypes.Structure):
@@ -380,6 +381,10 @@ def lib() -> ctypes.CDLL:
     L.qc_mlearner_grads.argtypes = [vp, P(QcDqnLayer)]
     L.qc_mlearner_apply.argtypes = [vp, P(QcDqnLayer)]
     L.qc_mlearner_states.argtypes = [vp, vp, vp, vp]
+    for kind in ("actor", "mactor", "replay", "learner", "mlearner"):
+        getattr(L, f"qc_{kind}_state_bytes").argtypes = [vp, P(u64)]
+        getattr(L, f"qc_{kind}_state_export").argtypes = [vp, vp, u64]
+        getattr(L, f"qc_{kind}_state_import").argtypes = [vp, vp, u64]
     if isinstance(L, _Tolerant):
         L = L.lib
     for name in EXPORTS:
@@ -447,11 +452,48 @@ class DeviceHandle:
         except Exception:
             pass
 
+    def _export_state(self):
+        """The handle's whole state (qc_<kind>_state_export) as a uint8 CPU tensor; synchronises its stream."""
+        import torch
+        self._bind_stream()
+        n = ctypes.c_uint64()
+        self._check(getattr(lib(), self._prefix + "_state_bytes")(self._h, ctypes.byref(n)))
+        blob = torch.empty(n.value, dtype=torch.uint8)
+        self._check(getattr(lib(), self._prefix + "_state_export")(self._h, ctypes.c_void_p(blob.data_ptr()), n.value))
+        return blob
+
+    def _import_state(self, blob):
+        """qc_<kind>_state_import of a tensor `_export_state` made; a refusal raises QCartError (QC_EINVAL) naming the
+        field that differs and leaves the handle as it was."""
+        import torch
+        if not isinstance(blob, torch.Tensor) or blob.dtype != torch.uint8 or blob.dim() != 1:
+            raise ValueError("the state blob must be a 1-d uint8 tensor")
+        blob = blob.cpu().contiguous()
+        self._bind_stream()
+        self._check(getattr(lib(), self._prefix + "_state_import")(self._h, ctypes.c_void_p(blob.data_ptr()),
+                                                                  blob.numel()))
+
     def _bind_stream(self):
         """Later launches of this handle go to torch's current stream of its device."""
         import torch
         s = torch.cuda.current_stream(self.device).cuda_stream
         self._check(getattr(lib(), self._prefix + "_set_stream")(self._h, ctypes.c_void_p(s)))
+
+
+def check_echo(who: str, state, mine: dict, payload=()):
+    """The refusal rule of every load_state_dict: `state` must carry each of `mine`'s fields with the same value
+    (the first that differs is named) and the payload keys."""
+    if not isinstance(state, dict):
+        raise ValueError(f"{who}: a state is a dict, not {type(state).__name__}")
+    for k, v in mine.items():
+        if k not in state:
+            raise ValueError(f"{who}: the state has no field {k!r} (made by another class?)")
+        got = tuple(state[k]) if isinstance(state[k], list) else state[k]
+        if got != v:
+            raise ValueError(f"{who}: {k} differs: the state was made for {state[k]!r}, this object for {v!r}")
+    for k in payload:
+        if k not in state:
+            raise ValueError(f"{who}: the state has no {k!r}")
 
 
 def fill_layer(slot: "QcDqnLayer", tensors) -> None:

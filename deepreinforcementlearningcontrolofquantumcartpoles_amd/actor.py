@@ -109,6 +109,32 @@ class _ActorHandle(L.DeviceHandle):
         return actions
 
 
+    def _made_for(self) -> dict:
+        raise NotImplementedError
+
+    def state_dict(self) -> dict:
+        """Everything the next `act` reads, as CPU values (checkpoint.save): the handle's blob (the prepared weights
+        as the kernels read them, which layers are noisy, the seed; qc_*_state_export) and the Philox call
+        `counter`. Synchronises the actor's stream."""
+        with torch.cuda.device(self.device):
+            blob = self._export_state()
+        return {"kind": self._prefix, **self._made_for(), "blob": blob, "counter": int(self.counter)}
+
+    def check_state_dict(self, state: dict):
+        """Raise ValueError naming the first field of `state` this actor was not made for; changes nothing. (The
+        library compares the blob's own header again on import.)"""
+        L.check_echo(type(self).__name__, state, {"kind": self._prefix, **self._made_for()}, ("blob", "counter"))
+
+    def load_state_dict(self, state: dict):
+        """Continue from a `state_dict()`: afterwards `act` gives bit for bit what the saved actor would have.
+        Refused (ValueError / QCartError, nothing changed) for an actor of another net or max_batch."""
+        self.check_state_dict(state)
+        with torch.cuda.device(self.device):
+            self._import_state(state["blob"])
+        self.counter = int(state["counter"])
+        self._keep = []
+
+
 class DQNActor(_ActorHandle):
     """Device-side action selection for B envs with a reference direct_DQN's parameters. hidden2: fc2's width,
     256 (the harmonic and inverted harmonic drivers' net) or 512 (the quartic and inverted quartic drivers');
@@ -125,6 +151,10 @@ class DQNActor(_ActorHandle):
         p.data_length, p.seed, p.hidden2 = self.data_length, int(seed), self.hidden2
         self._create(p, device, n_actions, max_batch)
         self.load(params)
+
+    def _made_for(self) -> dict:
+        return {"data_length": self.data_length, "n_actions": self.n_actions, "hidden2": self.hidden2,
+                "max_batch": self.max_batch}
 
     def load(self, params: Mapping[str, torch.Tensor]):
         """(Re)load fc1, fc2, fc31, fc41 from a state_dict (the trainer's periodic push,
@@ -220,6 +250,9 @@ class MeasurementActor(_ActorHandle):
         self._create(p, device, n_actions, max_batch)
         self.flat_len = int(L.lib().qc_mactor_flat_len(self._h))
         self.load(params)
+
+    def _made_for(self) -> dict:
+        return {"read_length": self.read_length, "n_actions": self.n_actions, "max_batch": self.max_batch}
 
     def load(self, params: Mapping[str, torch.Tensor]):
         layers = (L.QcDqnLayer * 6)()

@@ -66,6 +66,7 @@ class Stepper(L.DeviceHandle):
         self.N = L.lib().qc_dim(h)
         self.n_obs = L.lib().qc_n_obs(h)
         self.n_slots = physics.n_actions   # grows with add_force
+        self._forces = {}                  # slot -> force of the slots add_force made (state_dict)
 
     @property
     def state_dtype(self) -> torch.dtype:
@@ -148,7 +149,69 @@ class Stepper(L.DeviceHandle):
     def add_force(self, force: float) -> int:
         slot = L.check(L.lib().qc_add_force(self._h, float(force)), self._h)
         self.n_slots = max(self.n_slots, slot + 1)
+        if slot >= self.physics.n_actions:
+            self._forces[slot] = float(force)
         return slot
+
+    # ------------------------------------------------------------------ checkpoint
+    def _made_for(self) -> dict:
+        made = {"kind": "qc", "B": self.batch, "env_offset": self.env_offset, "xth": float(self._params.xth)}
+        made.update({"physics." + k: v for k, v in self.physics.asdict().items()})
+        return made
+
+    def state_dict(self) -> dict:
+        """What the next step() reads besides psi, as CPU values (checkpoint.save): the noise seed, every env's
+        Philox counter, the noise mode and (mt19937) every env's MT19937 state, the current dt and gamma
+        (set_dynamics) and the force slots add_force made; and what the stepper was made for (physics, B,
+        env_offset), which load_state_dict compares. Synchronises the stepper's stream."""
+        p = L.QcParams()
+        L.check(L.lib().qc_get_params(self._h, ctypes.byref(p)), self._h)
+        mode = self.noise_mode
+        return {**self._made_for(), "seed": int(p.seed), "step_counter": self.step_counter,
+                "env_counters": self.env_counters().cpu(), "noise_mode": mode,
+                "mt19937_state": self.mt19937_state().cpu() if mode == "mt19937" else None,
+                "dt": float(p.dt), "gamma": float(p.gamma), "forces": sorted(self._forces.items())}
+
+    def check_state_dict(self, state: dict):
+        """Raise ValueError naming the first thing in `state` this stepper cannot take: a field it was not made
+        for, or a force slot it already holds with another force. Changes nothing."""
+        L.check_echo("Stepper", state, self._made_for(),
+                    ("seed", "env_counters", "noise_mode", "mt19937_state", "dt", "gamma", "forces"))
+        if state["noise_mode"] not in ("philox", "mt19937"):
+            raise ValueError(f"Stepper: noise_mode {state['noise_mode']!r} is neither 'philox' nor 'mt19937'")
+        if tuple(state["env_counters"].shape) != (self.batch,):
+            raise ValueError(f"Stepper: env_counters has shape {tuple(state['env_counters'].shape)}, not ({self.batch},)")
+        nxt = self.n_slots
+        for slot, force in state["forces"]:
+            if slot in self._forces:
+                if self._forces[slot] != force:
+                    raise ValueError(f"Stepper: force slot {slot} differs: the state holds {force!r}, this stepper "
+                                     f"already {self._forces[slot]!r}")
+            elif slot != nxt:
+                raise ValueError(f"Stepper: force slot {slot} differs: the state's force {force!r} would land in "
+                                 f"slot {nxt} of this stepper")
+            else:
+                nxt += 1
+
+    def load_state_dict(self, state: dict):
+        """Re-apply a `state_dict()`: the dynamics and the missing force slots, the seed, the noise mode with its
+        streams, the counters. Refused with a ValueError, before anything changes, for a stepper made for other
+        physics, B or env_offset, or one whose own force slots conflict."""
+        self.check_state_dict(state)
+        p = L.QcParams()
+        L.check(L.lib().qc_get_params(self._h, ctypes.byref(p)), self._h)
+        if (p.dt, p.gamma) != (state["dt"], state["gamma"]):
+            self.set_dynamics(state["dt"], state["gamma"])
+        for slot, force in state["forces"]:
+            if slot not in self._forces and self.add_force(force) != slot:
+                raise RuntimeError(f"Stepper: add_force({force!r}) did not give slot {slot}")
+        if int(p.seed) != state["seed"] or (self.noise_mode == "mt19937" and state["noise_mode"] == "philox"):
+            self.set_seed(state["seed"])   # (also: back to the Philox mode)
+        if state["noise_mode"] == "mt19937":
+            if self.noise_mode != "mt19937":
+                self.set_seed_mt19937(0)   # allocates the streams; their words follow
+            self.mt19937_state(state["mt19937_state"])
+        self.env_counters(state["env_counters"])
 
     def group_layout(self):
         """(single-slot workgroups, two-slot workgroups) of the last grouped step() call: int32 numpy arrays

@@ -508,6 +508,7 @@ struct ActorCore {
     int64_t max_batch = 0;       // also the noise buffer's leading dimension
     uint64_t seed = 0;
     float* d_w = nullptr;        // all fragments + padded biases
+    size_t w_floats = 0;         // its length
     float* d_noise = nullptr;    // [noise_len][max_batch]
     Layer L[4]{};                // k_actor_act's layers (s / sb null where loaded without sigma)
 };
@@ -612,6 +613,7 @@ int qc_actor_create(const qc_dqn_params* p, int device, qc_actor** out) {
     const bool noisy[4] = {true, true, true, true};
     const size_t floats = frag_layout(4, O, K, noisy, a->off_u, a->off_s, a->off_ub, a->off_sb);
     Dev g(device);
+    a->w_floats = floats;
     hipError_t e = hipMalloc(&a->d_w, floats * sizeof(float));
     if (e == hipSuccess) e = hipMemset(a->d_w, 0, floats * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(&a->d_noise, (size_t)a->noise_len * (size_t)p->max_batch * sizeof(float));
@@ -732,6 +734,7 @@ int qc_mactor_create(const qc_mdqn_params* p, int device, qc_mactor** out) {
     const size_t floats = frag_layout(6, O, K, noisy, a->off_w, a->off_s, a->off_b, a->off_sb);
     Dev g(device);
     const size_t mb = (size_t)p->max_batch, ch = (size_t)a->chunk;
+    a->w_floats = floats;
     hipError_t e = hipMalloc(&a->d_w, floats * sizeof(float));
     if (e == hipSuccess) e = hipMemset(a->d_w, 0, floats * sizeof(float));
     if (e == hipSuccess) e = hipMalloc(&a->d_y1, ch * kC1 * a->T1 * sizeof(float));
@@ -832,6 +835,139 @@ int qc_mactor_act(qc_mactor* a, int64_t B, int64_t env_offset, const float* obs,
     k.h_ld = ld;
     return act_tail(a, k, "measurement actor launch", B, env_offset, noisy, noise, eps, counter, actions, q_out,
                     random_out);
+}
+
+}  // extern "C"
+
+// ---- exported state of both actors (the blob's header: qcart_state.hpp). An actor holds no natural-layout weights,
+// so the payload is d_w as it is (the effective weights' fragments and the padded biases, for the measurement
+// actor the convolutions' too), which of k_actor_act's four layers carry sigma fragments, and the seed. The seed is
+// state, not geometry: an import takes the blob's.
+namespace {
+namespace st = qcart::state;
+struct ActorHead {
+    uint64_t seed;
+    uint32_t sigma_mask;   // bit l: L[l].s / L[l].sb are set
+    uint32_t pad;
+};
+
+st::Header actor_header(const qc_actor& a) {
+    st::Header h = st::make(st::kActor);
+    st::put_i(h, "data_length", a.p.data_length);
+    st::put_i(h, "n_actions", a.n_act);
+    st::put_i(h, "hidden2", a.w2);
+    st::put_i(h, "max_batch", a.max_batch);
+    st::put_i(h, "weight_floats", (int64_t)a.w_floats);
+    h.payload_bytes = sizeof(ActorHead) + a.w_floats * sizeof(float);
+    return h;
+}
+st::Header mactor_header(const qc_mactor& a) {
+    st::Header h = st::make(st::kMactor);
+    st::put_i(h, "read_length", a.p.read_length);
+    st::put_i(h, "n_actions", a.n_act);
+    st::put_i(h, "max_batch", a.max_batch);
+    st::put_i(h, "chunk", a.chunk);
+    st::put_i(h, "weight_floats", (int64_t)a.w_floats);
+    h.payload_bytes = sizeof(ActorHead) + a.w_floats * sizeof(float);
+    return h;
+}
+
+int actor_state_bytes(ActorCore* a, const st::Header& h, uint64_t* n) {
+    Dev g(a->device);
+    const hipError_t e = hipStreamSynchronize(a->stream);
+    if (e != hipSuccess) return hip_fail(a->err, e, "actor state_bytes");
+    *n = sizeof(st::Header) + h.payload_bytes;
+    return QC_OK;
+}
+
+int actor_state_export(ActorCore* a, const st::Header& h, void* dst, uint64_t n) {
+    const std::string who = std::string(st::kind_name(h.kind)) + "_state_export: ";
+    if (!a->loaded) { a->err = who + "no weights have been loaded: there is no state to save"; return QC_EINVAL; }
+    if (n != sizeof(st::Header) + h.payload_bytes) {
+        a->err = who + "n is " + std::to_string(n) + ", state_bytes gives " +
+                 std::to_string(sizeof(st::Header) + h.payload_bytes);
+        return QC_EINVAL;
+    }
+    ActorHead s{};
+    s.seed = a->seed;
+    for (int l = 0; l < 4; ++l)
+        if (a->L[l].s) s.sigma_mask |= 1u << l;
+    std::memcpy(dst, &h, sizeof(h));
+    st::Cursor cur(dst);
+    std::memcpy(cur.take(sizeof(s)), &s, sizeof(s));
+    Dev g(a->device);
+    hipError_t e = hipStreamSynchronize(a->stream);
+    if (e == hipSuccess) e = hipMemcpy(cur.take(a->w_floats * sizeof(float)), a->d_w, a->w_floats * sizeof(float), hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return hip_fail(a->err, e, "actor state export");
+    return QC_OK;
+}
+
+// validates, then copies d_w in; *head: the payload's head for the caller to rebuild L from
+int actor_state_import(ActorCore* a, const st::Header& mine, const void* src, uint64_t n, ActorHead* head) {
+    st::Header h;
+    std::string bad = st::validate(src, n, mine, &h);
+    if (bad.empty() && h.payload_bytes != mine.payload_bytes)
+        bad = std::string(st::kind_name(mine.kind)) + "_state_import: payload_bytes: blob " +
+              std::to_string(h.payload_bytes) + ", handle " + std::to_string(mine.payload_bytes);
+    if (bad.empty()) {
+        std::memcpy(head, (const unsigned char*)src + sizeof(st::Header), sizeof(*head));
+        if (head->sigma_mask > 15u || head->pad != 0)
+            bad = std::string(st::kind_name(mine.kind)) + "_state_import: sigma_mask: blob " +
+                  std::to_string(head->sigma_mask) + ", expected below 16";
+    }
+    if (!bad.empty()) { a->err = bad; return QC_EINVAL; }
+    Dev g(a->device);
+    hipError_t e = hipStreamSynchronize(a->stream);
+    if (e == hipSuccess)
+        e = hipMemcpy(a->d_w, (const unsigned char*)src + sizeof(st::Header) + sizeof(ActorHead),
+                      a->w_floats * sizeof(float), hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hip_fail(a->err, e, "actor state import");
+    a->seed = head->seed;
+    a->loaded = true;
+    return QC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int qc_actor_state_bytes(qc_actor* a, uint64_t* n) { return a && n ? actor_state_bytes(a, actor_header(*a), n) : QC_EINVAL; }
+
+int qc_actor_state_export(qc_actor* a, void* host_dst, uint64_t n) {
+    return a && host_dst ? actor_state_export(a, actor_header(*a), host_dst, n) : QC_EINVAL;
+}
+
+int qc_actor_state_import(qc_actor* a, const void* host_src, uint64_t n) {
+    if (!a) return QC_EINVAL;
+    ActorHead s{};
+    if (const int rc = actor_state_import(a, actor_header(*a), host_src, n, &s)) return rc;
+    a->p.seed = s.seed;
+    float* w = a->d_w;
+    for (int l = 0; l < 4; ++l) {
+        const bool sigma = (s.sigma_mask >> l & 1) != 0;
+        a->L[l] = Layer{w + a->off_u[l], sigma ? w + a->off_s[l] : nullptr, w + a->off_ub[l],
+                        sigma ? w + a->off_sb[l] : nullptr};
+    }
+    return QC_OK;
+}
+
+int qc_mactor_state_bytes(qc_mactor* a, uint64_t* n) { return a && n ? actor_state_bytes(a, mactor_header(*a), n) : QC_EINVAL; }
+
+int qc_mactor_state_export(qc_mactor* a, void* host_dst, uint64_t n) {
+    return a && host_dst ? actor_state_export(a, mactor_header(*a), host_dst, n) : QC_EINVAL;
+}
+
+int qc_mactor_state_import(qc_mactor* a, const void* host_src, uint64_t n) {
+    if (!a) return QC_EINVAL;
+    ActorHead s{};
+    if (const int rc = actor_state_import(a, mactor_header(*a), host_src, n, &s)) return rc;
+    a->p.seed = s.seed;
+    float* w = a->d_w;
+    for (int l = 4; l < 6; ++l) {   // fc21 / fc31 are k_actor_act's layers 2 / 3 (qc_mactor_load)
+        const bool sigma = (s.sigma_mask >> (l - 2) & 1) != 0;
+        a->L[l - 2] = Layer{w + a->off_w[l], sigma ? w + a->off_s[l] : nullptr, w + a->off_b[l],
+                            sigma ? w + a->off_sb[l] : nullptr};
+    }
+    return QC_OK;
 }
 
 }  // extern "C"

@@ -833,6 +833,139 @@ int stats_core(LearnerCore& c, qc_learner_stats_t* out) {
     return QC_OK;
 }
 
+// ---- exported state ----
+namespace {
+// the payload's head; the device buffers follow in state_parts' order
+struct StateHead {
+    int64_t updates, step;
+    double lr, l1, l2;
+    int32_t backup_counter, pad;
+    int32_t cnt[2];   // d_cnt: non-finite losses, the out-of-range-action flag
+};
+struct StatePart {
+    void* p;
+    size_t bytes;
+};
+// F, FT and d_norm are saved as they are: a copy is bitwise by construction, whereas rebuilding them would run
+// k_learner_prep (and the measurement learner's own preparation behind it) on P and on PT
+int state_parts(const LearnerCore& c, StatePart* out) {
+    const size_t pb = (size_t)c.np * sizeof(float);
+    int n = 0;
+    for (float* q : {c.P, c.PT, c.E, c.V, c.MU}) out[n++] = StatePart{q, pb};
+    out[n++] = StatePart{c.F, (size_t)c.nf * sizeof(float)};
+    out[n++] = StatePart{c.FT, (size_t)c.nf_fwd * sizeof(float)};
+    out[n++] = StatePart{c.d_norm, kMaxWN * sizeof(float)};
+    return n;
+}
+uint64_t state_payload(const LearnerCore& c) {
+    StatePart part[8];
+    const int n = state_parts(c, part);
+    uint64_t b = sizeof(StateHead);
+    for (int i = 0; i < n; ++i) b += part[i].bytes;
+    return b;
+}
+}  // namespace
+
+void put_core_fields(const LearnerCore& c, state::Header& h) {
+    state::put_i(h, "n_actions", c.A);
+    state::put_i(h, "batch_size", c.B);
+    state::put_i(h, "backup_period", c.backup_period);
+    state::put_i(h, "target_mode", c.target_mode);
+    state::put_f(h, "gamma", c.gamma);
+    state::put_f(h, "alive_reward", c.alive_reward);
+    state::put_f(h, "failing_reward", c.failing_reward);
+    state::put_f(h, "beta1", c.b1);
+    state::put_f(h, "beta2", c.b2);
+    state::put_u(h, "seed", c.seed);
+    state::put_i(h, "param_floats", c.np);
+    state::put_i(h, "fragment_floats", c.nf);
+    state::put_i(h, "target_frag_floats", c.nf_fwd);
+    h.payload_bytes = state_payload(c);
+}
+
+int state_bytes_core(LearnerCore& c, uint64_t* n) {
+    host::Dev g(c.device);
+    const hipError_t e = hipStreamSynchronize(c.stream);
+    if (e != hipSuccess) return host::hip_fail(c.err, e, "learner state_bytes");
+    *n = sizeof(state::Header) + state_payload(c);
+    return QC_OK;
+}
+
+int state_export_core(LearnerCore& c, state::Header h, void* host_dst, uint64_t n) {
+    if (!c.loaded) {
+        c.err = std::string(c.name) + "_state_export: " + c.name + "_load has not been called: there is no state to save";
+        return QC_EINVAL;
+    }
+    if (n != sizeof(state::Header) + h.payload_bytes) {
+        c.err = std::string(c.name) + "_state_export: n is " + std::to_string(n) + ", " + c.name + "_state_bytes gives " +
+                std::to_string(sizeof(state::Header) + h.payload_bytes);
+        return QC_EINVAL;
+    }
+    host::Dev g(c.device);
+    StateHead s{};
+    s.updates = c.updates; s.step = c.step;
+    s.lr = c.lr; s.l1 = c.l1; s.l2 = c.l2;
+    s.backup_counter = c.backup_counter;
+    hipError_t e = hipStreamSynchronize(c.stream);
+    if (e == hipSuccess) e = hipMemcpy(s.cnt, c.d_cnt, sizeof(s.cnt), hipMemcpyDeviceToHost);
+    std::memcpy(host_dst, &h, sizeof(h));
+    state::Cursor cur(host_dst);
+    std::memcpy(cur.take(sizeof(s)), &s, sizeof(s));
+    StatePart part[8];
+    const int np = state_parts(c, part);
+    for (int i = 0; i < np; ++i) {
+        unsigned char* at = cur.take(part[i].bytes);
+        if (e == hipSuccess) e = hipMemcpy(at, part[i].p, part[i].bytes, hipMemcpyDeviceToHost);
+    }
+    if (e != hipSuccess) return host::hip_fail(c.err, e, "learner state export");
+    return QC_OK;
+}
+
+int state_import_core(LearnerCore& c, const state::Header& mine, const void* host_src, uint64_t n) {
+    state::Header h;
+    std::string bad = state::validate(host_src, n, mine, &h);
+    if (bad.empty() && h.payload_bytes != mine.payload_bytes)
+        bad = std::string(c.name) + "_state_import: payload_bytes: blob " + std::to_string(h.payload_bytes) +
+              ", handle " + std::to_string(mine.payload_bytes);
+    StateHead s{};
+    if (bad.empty()) {
+        std::memcpy(&s, (const unsigned char*)host_src + sizeof(state::Header), sizeof(s));
+        const std::string who = std::string(c.name) + "_state_import: ";
+        if (s.backup_counter < 0 || s.backup_counter >= c.backup_period)
+            bad = who + "backup_counter: blob " + std::to_string(s.backup_counter) + ", handle's backup_period " +
+                  std::to_string(c.backup_period);
+        else if (s.step < 0 || s.updates < 0)
+            bad = who + "step / updates: blob " + std::to_string(s.step) + " / " + std::to_string(s.updates) +
+                  ", expected >= 0";
+        else if (!(s.lr >= 0.))
+            bad = who + "lr: blob " + std::to_string(s.lr) + ", expected >= 0";
+    }
+    if (!bad.empty()) {
+        c.err = bad;
+        return QC_EINVAL;
+    }
+    host::Dev g(c.device);
+    hipError_t e = hipStreamSynchronize(c.stream);
+    state::Cursor cur(const_cast<void*>(host_src));
+    cur.take(sizeof(s));
+    StatePart part[8];
+    const int np = state_parts(c, part);
+    for (int i = 0; i < np; ++i) {
+        const unsigned char* at = cur.take(part[i].bytes);
+        if (e == hipSuccess) e = hipMemcpy(part[i].p, at, part[i].bytes, hipMemcpyHostToDevice);
+    }
+    if (e == hipSuccess) e = hipMemcpy(c.d_cnt, s.cnt, sizeof(s.cnt), hipMemcpyHostToDevice);
+    // the gradients of the last update are introspection only (every update writes all of G before it reads it)
+    if (e == hipSuccess) e = hipMemsetAsync(c.G, 0, (size_t)c.np * sizeof(float), c.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c.stream);
+    if (e != hipSuccess) return host::hip_fail(c.err, e, "learner state import");
+    c.updates = s.updates; c.step = s.step;
+    c.lr = s.lr; c.l1 = s.l1; c.l2 = s.l2;
+    c.backup_counter = s.backup_counter;
+    c.loaded = true;
+    return QC_OK;
+}
+
 }  // namespace learner
 }  // namespace qcart
 
@@ -985,5 +1118,23 @@ int qc_learner_update(qc_learner* l, const float* transitions, const float* is_w
 int qc_learner_apply(qc_learner* l, const qc_dqn_layer grads[6]) { return l && grads ? apply_core(*l, grads) : QC_EINVAL; }
 
 int qc_learner_stats(qc_learner* l, qc_learner_stats_t* out) { return l && out ? stats_core(*l, out) : QC_EINVAL; }
+
+static qcart::state::Header learner_header(const qc_learner& l) {
+    qcart::state::Header h = qcart::state::make(qcart::state::kLearner);
+    qcart::state::put_i(h, "data_length", l.k.in_len);
+    qcart::state::put_i(h, "hidden2", l.w2);
+    put_core_fields(l, h);
+    return h;
+}
+
+int qc_learner_state_bytes(qc_learner* l, uint64_t* n) { return l && n ? state_bytes_core(*l, n) : QC_EINVAL; }
+
+int qc_learner_state_export(qc_learner* l, void* host_dst, uint64_t n) {
+    return l && host_dst ? state_export_core(*l, learner_header(*l), host_dst, n) : QC_EINVAL;
+}
+
+int qc_learner_state_import(qc_learner* l, const void* host_src, uint64_t n) {
+    return l ? state_import_core(*l, learner_header(*l), host_src, n) : QC_EINVAL;
+}
 
 }  // extern "C"

@@ -14,6 +14,7 @@
 
 #include "../../include/qcart.h"
 #include "qcart_dqn.hpp"
+#include "qcart_state.hpp"
 
 namespace qcart {
 namespace learner {
@@ -234,6 +235,15 @@ void opt_step(LearnerCore& c, int chain);
 // qc_*_apply up to and including opt_step
 int apply_core(LearnerCore& c, const qc_dqn_layer* grads);
 int stats_core(LearnerCore& c, qc_learner_stats_t* out);
+
+// ---- qc_*_state_bytes / _export / _import of both learners (the blob's header: qcart_state.hpp). The payload is
+// the host schedule (updates, step, backup_counter, lr, l1, l2), the device counters behind qc_*_stats, then P, PT,
+// E, V, MU, F, FT and d_norm as they are. The handle passes its own header: its geometry fields first;
+// put_core_fields appends what both params structs share and the buffer sizes
+void put_core_fields(const LearnerCore& c, state::Header& h);
+int state_bytes_core(LearnerCore& c, uint64_t* n);
+int state_export_core(LearnerCore& c, state::Header h, void* host_dst, uint64_t n);
+int state_import_core(LearnerCore& c, const state::Header& mine, const void* host_src, uint64_t n);
 
 }  // namespace learner
 

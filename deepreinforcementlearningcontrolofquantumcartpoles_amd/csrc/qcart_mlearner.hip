@@ -657,5 +657,26 @@ int qc_mlearner_apply(qc_mlearner* l, const qc_dqn_layer grads[8]) {
 
 int qc_mlearner_stats(qc_mlearner* l, qc_learner_stats_t* out) { return l && out ? stats_core(*l, out) : QC_EINVAL; }
 
+// F holds the convolutions' fragments (and, weight-normalised, their effective weights) behind the tail's, so
+// the core's payload covers what k_mlearner_prep made
+static qcart::state::Header mlearner_header(const qc_mlearner& l) {
+    qcart::state::Header h = qcart::state::make(qcart::state::kMlearner);
+    qcart::state::put_i(h, "read_length", l.L);
+    qcart::state::put_i(h, "read_step_length", l.m);
+    qcart::state::put_i(h, "conv_weight_norm", l.cwn ? 1 : 0);
+    put_core_fields(l, h);
+    return h;
+}
+
+int qc_mlearner_state_bytes(qc_mlearner* l, uint64_t* n) { return l && n ? state_bytes_core(*l, n) : QC_EINVAL; }
+
+int qc_mlearner_state_export(qc_mlearner* l, void* host_dst, uint64_t n) {
+    return l && host_dst ? state_export_core(*l, mlearner_header(*l), host_dst, n) : QC_EINVAL;
+}
+
+int qc_mlearner_state_import(qc_mlearner* l, const void* host_src, uint64_t n) {
+    return l ? state_import_core(*l, mlearner_header(*l), host_src, n) : QC_EINVAL;
+}
+
 }  // extern "C"
 

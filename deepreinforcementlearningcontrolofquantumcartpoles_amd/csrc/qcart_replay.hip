@@ -22,11 +22,13 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <string>
 
 #include "../../include/qcart.h"
 #include "qcart_host.hpp"
 #include "qcart_kernels.hpp"
+#include "qcart_state.hpp"
 
 namespace qcart {
 namespace replay {
@@ -614,6 +616,128 @@ int qc_replay_buffers(const qc_replay* r, const double** tree, const float** dat
     if (!r) return QC_EINVAL;
     if (tree) *tree = r->tree;
     if (data) *data = r->data;
+    return QC_OK;
+}
+
+}  // extern "C"
+
+// ---- exported state (the blob's header: qcart_state.hpp). Payload: ReplayHead, the whole tree, then the first
+// `rows` rows. rows < capacity only where State proves that no row at or past State.len was ever written: every add
+// so far was sequential (the 'sequential' policy, or passes < 1) and the ring has not wrapped (len < capacity);
+// otherwise all rows. The owner tags are not saved: a store only raises a slot's tag (atomicMax) to one of its own
+// epoch, which is above every tag of an earlier epoch, so an import zeroes them and State.epoch carries on.
+namespace {
+namespace st = qcart::state;
+struct ReplayHead {
+    double beta;
+    uint64_t sample_ctr;
+    int64_t rows;
+    State s;
+};
+
+st::Header replay_header(const qc_replay& r) {
+    const qc_replay_params& p = r.p;
+    st::Header h = st::make(st::kReplay);
+    st::put_i(h, "capacity", p.capacity);
+    st::put_i(h, "row_len", p.row_len);
+    st::put_i(h, "policy", p.policy);
+    st::put_f(h, "passes_before_random", p.passes_before_random);
+    st::put_f(h, "alpha", p.alpha);
+    st::put_f(h, "beta", p.beta);
+    st::put_f(h, "beta_increment", p.beta_increment);
+    st::put_f(h, "abs_err_upper", p.abs_err_upper);
+    st::put_f(h, "epsilon_scale", p.epsilon_scale);
+    st::put_u(h, "seed", p.seed);
+    return h;
+}
+
+int64_t rows_to_save(const qc_replay& r, const State& s) {
+    const bool all_sequential = r.p.policy == 0 || s.passes < 1.0;
+    return all_sequential && s.len < r.p.capacity ? s.len : r.p.capacity;
+}
+uint64_t replay_payload(const qc_replay& r, int64_t rows) {
+    return sizeof(ReplayHead) + (uint64_t)r.tree_size * sizeof(double) +
+           (uint64_t)rows * (uint64_t)r.p.row_len * sizeof(float);
+}
+// the handle's State after everything queued on its stream
+int read_state(qc_replay* r, State* s) {
+    if (hipStreamSynchronize(r->stream) != hipSuccess ||
+        hipMemcpy(s, r->st, sizeof(State), hipMemcpyDeviceToHost) != hipSuccess)
+        return rfail(r, QC_EHIP, "replay state copy failed");
+    return QC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int qc_replay_state_bytes(qc_replay* r, uint64_t* n) {
+    if (!r || !n) return QC_EINVAL;
+    Dev g(r->device);
+    State s{};
+    if (const int rc = read_state(r, &s)) return rc;
+    *n = sizeof(st::Header) + replay_payload(*r, rows_to_save(*r, s));
+    return QC_OK;
+}
+
+int qc_replay_state_export(qc_replay* r, void* host_dst, uint64_t n) {
+    if (!r || !host_dst) return QC_EINVAL;
+    Dev g(r->device);
+    ReplayHead hd{};
+    if (const int rc = read_state(r, &hd.s)) return rc;
+    hd.beta = r->beta;
+    hd.sample_ctr = r->sample_ctr;
+    hd.rows = rows_to_save(*r, hd.s);
+    st::Header h = replay_header(*r);
+    h.payload_bytes = replay_payload(*r, hd.rows);
+    if (n != sizeof(st::Header) + h.payload_bytes)
+        return rfail(r, QC_EINVAL, "qc_replay_state_export: n differs from what qc_replay_state_bytes gives now");
+    std::memcpy(host_dst, &h, sizeof(h));
+    st::Cursor cur(host_dst);
+    std::memcpy(cur.take(sizeof(hd)), &hd, sizeof(hd));
+    const size_t tb = (size_t)r->tree_size * sizeof(double), db = (size_t)hd.rows * r->p.row_len * sizeof(float);
+    hipError_t e = hipMemcpy(cur.take(tb), r->tree, tb, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && db) e = hipMemcpy(cur.take(db), r->data, db, hipMemcpyDeviceToHost);
+    return e == hipSuccess ? QC_OK : rfail(r, QC_EHIP, "replay state export failed");
+}
+
+int qc_replay_state_import(qc_replay* r, const void* host_src, uint64_t n) {
+    if (!r) return QC_EINVAL;
+    st::Header h;
+    std::string bad = st::validate(host_src, n, replay_header(*r), &h);
+    ReplayHead hd{};
+    const std::string who = "qc_replay_state_import: ";
+    const int64_t cap = r->p.capacity;
+    if (bad.empty() && h.payload_bytes < sizeof(ReplayHead))
+        bad = who + "payload_bytes: blob " + std::to_string(h.payload_bytes) + ", the payload's head alone has " +
+              std::to_string(sizeof(ReplayHead));
+    if (bad.empty()) {
+        std::memcpy(&hd, (const unsigned char*)host_src + sizeof(st::Header), sizeof(hd));
+        if (hd.s.len < 0 || hd.s.len > cap || hd.s.ptr < 0 || hd.s.ptr >= cap)
+            bad = who + "len / data_pointer: blob " + std::to_string(hd.s.len) + " / " + std::to_string(hd.s.ptr) +
+                  ", handle's capacity " + std::to_string(cap);
+        else if (hd.rows != rows_to_save(*r, hd.s))
+            bad = who + "rows: blob " + std::to_string(hd.rows) + ", its State implies " +
+                  std::to_string(rows_to_save(*r, hd.s));
+        else if (h.payload_bytes != replay_payload(*r, hd.rows))
+            bad = who + "payload_bytes: blob " + std::to_string(h.payload_bytes) + ", handle " +
+                  std::to_string(replay_payload(*r, hd.rows));
+    }
+    if (!bad.empty()) return rfail(r, QC_EINVAL, bad);
+    Dev g(r->device);
+    const unsigned char* at = (const unsigned char*)host_src + sizeof(st::Header) + sizeof(ReplayHead);
+    const size_t tb = (size_t)r->tree_size * sizeof(double), rb = (size_t)r->p.row_len * sizeof(float);
+    const size_t db = (size_t)hd.rows * rb;
+    hipError_t e = hipStreamSynchronize(r->stream);
+    if (e == hipSuccess) e = hipMemcpy(r->tree, at, tb, hipMemcpyHostToDevice);
+    if (e == hipSuccess && db) e = hipMemcpy(r->data, at + tb, db, hipMemcpyHostToDevice);
+    if (e == hipSuccess && hd.rows < cap)   // never written: as qc_replay_create leaves them
+        e = hipMemsetAsync((unsigned char*)r->data + db, 0, (size_t)(cap - hd.rows) * rb, r->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(r->owner, 0, (size_t)cap * sizeof(unsigned long long), r->stream);
+    if (e == hipSuccess) e = hipMemcpy(r->st, &hd.s, sizeof(State), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
+    if (e != hipSuccess) return rfail(r, QC_EHIP, "replay state import failed");
+    r->beta = hd.beta;
+    r->sample_ctr = hd.sample_ctr;
     return QC_OK;
 }
 

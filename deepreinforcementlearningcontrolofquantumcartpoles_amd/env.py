@@ -119,6 +119,14 @@ class BatchedEnv:
         if reset == "deferred" and not auto_reset:
             raise ValueError("reset='deferred' is an auto-reset mode (HO, IHO, IQO): it needs auto_reset")
         self.reset_mode = reset
+        # what a state_dict echoes and load_state_dict compares (the stepper and the record add their own)
+        self._made = {"kind": "BatchedEnv", "family": physics.family, "B": self.B, "env_offset": int(env_offset),
+                      "input": input, "reset": reset, "reset_kind": reset_kind, "seed": int(seed),
+                      "auto_reset": bool(auto_reset), "input_scaling": float(input_scaling),
+                      "failing_reward": float(failing_reward), "reward_multiply": float(reward_multiply),
+                      "t_max": float(t_max), "phonon_cutoff": float(phonon_cutoff),
+                      "energy_cutoff": float(energy_cutoff), "init_energy_cutoff": float(init_energy_cutoff),
+                      "init_time": self.init_time}
         self._pending = torch.zeros(self.B, dtype=torch.uint8, device=self.dev)
         self._calls = 0
         self.rec = None
@@ -441,6 +449,75 @@ class BatchedEnv:
             if self.auto_reset:
                 self.reset(done)
         return self.obs, reward.to(torch.float32), done, info
+
+    # ------------------------------------------------------------------ checkpoint
+    _WARM = ("_warm_left", "_warm_fail", "_draws", "_k", "_budget", "_mean0", "_std1")
+
+    def _state_tensors(self) -> list:
+        names = ["psi", "_pending", "t", "steps", "last_action", "episode_return", "_fin", "_fin_n"]
+        if self.rec is None:
+            names.append("obs")    # ('measurements': obs is the record's hist)
+        else:
+            names.append("rows")
+        if self.reset_mode == "warmup":
+            names += self._WARM
+        return names
+
+    def _made_for(self) -> dict:
+        return {**self._made, "read_length": self.rec.read_length if self.rec is not None else None}
+
+    def state_dict(self) -> dict:
+        """The whole env as CPU values (checkpoint.save): psi and every per-env tensor (pending resets, episode time,
+        steps and return, last action, the observation or the measurement rows, the warm-up mode's draw state), the
+        finished-episode ring with its write and read positions (so that finished_returns reports no episode twice;
+        the list of already-read ones is the caller's and is not saved), the call count, the torch generator of the
+        immediate mode's resets, the record's and the stepper's state; and what the env was made for, which
+        load_state_dict compares. Synchronises the device."""
+        st = dict(self._made_for())
+        for name in self._state_tensors():
+            st[name] = getattr(self, name).cpu()
+        st["_fin_read"] = int(self._fin_read)
+        st["_calls"] = int(self._calls)
+        st["generator"] = self.gen.get_state().cpu()
+        st["record"] = self.rec.state_dict() if self.rec is not None else None
+        st["stepper"] = self.st.state_dict()
+        return st
+
+    def check_state_dict(self, state: dict):
+        """Raise ValueError naming the first field of `state` this env was not made for (family and physics, B,
+        env_offset, input, reset mode, reset_kind, read_length, seed, the episode rules), or a tensor of another
+        shape. Changes nothing."""
+        names = self._state_tensors()
+        L.check_echo("BatchedEnv", state, self._made_for(),
+                    names + ["_fin_read", "_calls", "generator", "record", "stepper"])
+        self.st.check_state_dict(state["stepper"])
+        if self.rec is not None:
+            self.rec.check_state_dict(state["record"])
+        for name in names:
+            have, got = getattr(self, name), state[name]
+            if got.shape != have.shape or got.dtype != have.dtype:
+                raise ValueError(f"BatchedEnv: {name} is {got.dtype} {tuple(got.shape)}, not {have.dtype} "
+                                 f"{tuple(have.shape)}")
+
+    def load_state_dict(self, state: dict):
+        """Continue from a `state_dict()`: every later step() gives bit for bit what the saved env would have.
+        An env made with other arguments is refused with a ValueError naming the first difference, before anything
+        changes (nothing is converted: not the batch, the input, the reset mode or env_offset)."""
+        self.check_state_dict(state)
+        self.st.load_state_dict(state["stepper"])
+        if self.rec is not None:
+            self.rec.load_state_dict(state["record"])
+        for name in self._state_tensors():
+            have = getattr(self, name)
+            if name in ("obs", "last_action", "t", "steps", "episode_return"):   # replaced, not written, by step()
+                setattr(self, name, state[name].to(self.dev))
+            else:
+                have.copy_(state[name])
+        self._fin_read = int(state["_fin_read"])
+        self._calls = int(state["_calls"])
+        self.gen.set_state(state["generator"])
+        if self.rec is not None:
+            self.obs = self.rec.hist
 
     def analytic_actions(self, strategy: str = "LQG", con_parameter: float = 0.0) -> torch.Tensor:
         """Actions of the reference's analytic baseline controllers for the current states (qc_control):

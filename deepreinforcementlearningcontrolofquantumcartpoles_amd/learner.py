@@ -94,6 +94,8 @@ class _Learner(L.DeviceHandle):
             torch.cuda.init()
             self._check(self._fn("create")(ctypes.byref(p), self.device.index, ctypes.byref(h)))
         self._h = h
+        self._made = {"gamma": p.gamma, "alive_reward": p.alive_reward, "failing_reward": p.failing_reward,
+                      "backup_period": p.backup_period, "seed": p.seed}   # what a train_state echoes besides the net
         self.noise_len = int(self._fn("noise_len")(h))
         self.counter = 0
         self.last_loss = torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -186,6 +188,33 @@ class _Learner(L.DeviceHandle):
             actor._bind_stream()
             check(load(actor._h, layers), actor._h)
 
+    def _made_for(self) -> dict:
+        raise NotImplementedError
+
+    def train_state(self) -> dict:
+        """Everything the next `update` reads, as CPU values (checkpoint.save) — `state_dict()` stays the weights
+        in the reference's keys. The handle's blob (online and target parameters, LaProp's three moment buffers,
+        the prepared fragments, updates, step, backup_counter, lr, l1, l2; qc_*_state_export) and the Philox call
+        `counter`. Synchronises the learner's stream."""
+        with torch.cuda.device(self.device):
+            blob = self._export_state()
+        return {"kind": self._prefix, **self._made_for(), "blob": blob, "counter": int(self.counter)}
+
+    def check_train_state(self, state: dict):
+        """Raise ValueError naming the first field of `state` this learner was not made for; changes nothing. (The
+        library compares the blob's own header, with gamma, the rewards, betas and seed, again on import.)"""
+        L.check_echo(type(self).__name__, state, {"kind": self._prefix, **self._made_for()}, ("blob", "counter"))
+
+    def load_train_state(self, state: dict):
+        """Continue from a `train_state()`: every later update, push and state_dict gives bit for bit what the saved
+        learner would have. A learner made with other parameters is refused (ValueError / QCartError, nothing
+        changed); the learning rate is state (`set_lr`) and is restored, not compared."""
+        self.check_train_state(state)
+        with torch.cuda.device(self.device):
+            self._import_state(state["blob"])
+        self.counter = int(state["counter"])
+        self._keep = []
+
     def stats(self) -> dict:
         """Synchronises. Raises QCartError if an update since the last call saw an out-of-range action."""
         s = L.QcLearnerStats()
@@ -220,6 +249,10 @@ class DQNLearner(_Learner):
         p = L.QcLearnerParams()
         p.data_length, p.hidden2 = self.data_length, self.hidden2
         self._create(p, params, gamma, lr, alive_reward, failing_reward, backup_period, seed)
+
+    def _made_for(self) -> dict:
+        return {"data_length": self.data_length, "n_actions": self.n_actions, "hidden2": self.hidden2,
+                "batch_size": self.batch_size, "target": self.target, "betas": self.betas, **self._made}
 
     def _layer_array(self, params: Mapping[str, torch.Tensor]):
         layers = self._layers()
@@ -315,6 +348,11 @@ class MeasurementLearner(_Learner):
         p.read_length, p.read_step_length = self.read_length, self.read_step_length
         p.conv_weight_norm = 1 if self.conv_weight_norm else 0
         self._create(p, params, gamma, lr, alive_reward, failing_reward, backup_period, seed)
+
+    def _made_for(self) -> dict:
+        return {"read_length": self.read_length, "read_step_length": self.read_step_length,
+                "n_actions": self.n_actions, "conv_weight_norm": bool(self.conv_weight_norm),
+                "batch_size": self.batch_size, "target": self.target, "betas": self.betas, **self._made}
 
     def _shapes(self):
         return [(o, i, k) for i, o, k, _ in M_CONV] + [(256, self.flat_len), (256, 256), (self.n_actions, 256),

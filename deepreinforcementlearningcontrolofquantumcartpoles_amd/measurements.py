@@ -50,6 +50,28 @@ class MeasurementRecord:
         self.hist = torch.zeros((B, 2, self.read_length), dtype=torch.float32, device=dev)
         self.forces = torch.zeros((B, self.K + 1), dtype=torch.float32, device=dev)
 
+    def _made_for(self) -> dict:
+        return {"kind": "MeasurementRecord", "B": self.st.batch, "read_length": self.read_length,
+                "coarse_grain": self.coarse_grain, "interval": self.interval, "input_scaling": self.input_scaling}
+
+    def state_dict(self) -> dict:
+        """hist and forces as CPU copies, and what the record was made for (checkpoint.save)."""
+        return {**self._made_for(), "hist": self.hist.cpu(), "forces": self.forces.cpu()}
+
+    def check_state_dict(self, state: dict):
+        L.check_echo("MeasurementRecord", state, self._made_for(), ("hist", "forces"))
+        for k in ("hist", "forces"):
+            if state[k].shape != getattr(self, k).shape or state[k].dtype != torch.float32:
+                raise ValueError(f"MeasurementRecord: {k} is {state[k].dtype} {tuple(state[k].shape)}, not float32 "
+                                 f"{tuple(getattr(self, k).shape)}")
+
+    def load_state_dict(self, state: dict):
+        """Continue from a `state_dict()` (in place: views of hist stay valid); another geometry is refused with a
+        ValueError before anything changes."""
+        self.check_state_dict(state)
+        self.hist.copy_(state["hist"])
+        self.forces.copy_(state["forces"])
+
     def record(self, q: torch.Tensor, actions: Optional[torch.Tensor] = None, default_action: Optional[int] = None,
                mode: Optional[torch.Tensor] = None, reward: Optional[torch.Tensor] = None,
                rows: Optional[torch.Tensor] = None) -> Optional[torch.Tensor]:

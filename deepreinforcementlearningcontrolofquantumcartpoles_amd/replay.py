@@ -48,6 +48,7 @@ class PrioritizedReplay(L.DeviceHandle):
         p.epsilon_scale = 1e-5
         p.seed = int(seed)
         self.capacity, self.data_size = int(capacity), int(data_size)
+        self._made = {"policy": policy, "passes_before_random": p.passes_before_random, "seed": p.seed}   # state echo
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             torch.cuda.init()
@@ -119,6 +120,29 @@ class PrioritizedReplay(L.DeviceHandle):
     @property
     def total_p(self) -> float:
         return float(self.stats()["total_p"])
+
+    def _made_for(self) -> dict:
+        return {"capacity": self.capacity, "data_size": self.data_size, **self._made}
+
+    def state_dict(self) -> dict:
+        """The whole memory as CPU values (checkpoint.save): the handle's blob (tree, rows, pointer, length, passes,
+        max, beta, the Philox counters; qc_replay_state_export) and `_len_ok`. One host buffer of about
+        capacity * (data_size * 4 + 16) bytes once the ring has filled; synchronises the memory's stream."""
+        with torch.cuda.device(self.device):
+            blob = self._export_state()
+        return {"kind": self._prefix, **self._made_for(), "blob": blob, "_len_ok": int(self._len_ok)}
+
+    def check_state_dict(self, state: dict):
+        """Raise ValueError naming the first field of `state` this memory was not made for; changes nothing."""
+        L.check_echo(type(self).__name__, state, {"kind": self._prefix, **self._made_for()}, ("blob", "_len_ok"))
+
+    def load_state_dict(self, state: dict):
+        """Continue from a `state_dict()`: stores, samples and updates then give bit for bit what the saved memory
+        would have. Another capacity, data_size, policy or seed is refused (nothing changed)."""
+        self.check_state_dict(state)
+        with torch.cuda.device(self.device):
+            self._import_state(state["blob"])
+        self._len_ok = int(state["_len_ok"])
 
     def buffers(self):
         """(tree float64 [tree_size], data float32 [capacity][data_size]) as device tensors (views)."""

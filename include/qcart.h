@@ -558,6 +558,51 @@ int qc_mlearner_apply(qc_mlearner* l, const qc_dqn_layer grads[8]);
 /* tests: the assembled states of a batch, next_out / prev_out [B][2][L] */
 int qc_mlearner_states(qc_mlearner* l, const float* transitions, float* next_out, float* prev_out);
 
+/* ---- checkpoint: export / import of a handle's whole state --------------------------------------------------
+ * For each of the five handle kinds that hold state of their own: qc_<kind>_state_bytes gives the size n of the
+ * handle's state as one host buffer now, qc_<kind>_state_export writes it (n as returned; QC_EINVAL on another n),
+ * qc_<kind>_state_import reads it back into a handle created with the same params, after which every later call
+ * gives bit for bit what it would have given on the exporting handle. All three synchronise the handle's stream
+ * (export and import also copy between host and device before they return); host_dst / host_src are host
+ * pointers. The stepper (qc_handle) needs none: qc_get_step_counter / qc_set_step_counter, qc_env_counters,
+ * qc_mt19937_state, qc_noise_mode, qc_set_dynamics and qc_add_force expose its state.
+ *
+ * A blob is a fixed-size header and a payload. The header carries a magic, the blob format version, the handle
+ * kind, the payload length and, as named fields, the handle's create-time params and the geometry derived from
+ * them. Import compares every field with the receiving handle (device and stream are not part of it) and returns
+ * QC_EINVAL on the first difference, qc_<kind>_last_error naming the field and both values; a truncated or padded
+ * buffer, a wrong magic or kind and a newer format version are refused the same way. A refused import leaves the
+ * handle exactly as it was. Importing into a handle whose qc_<kind>_load was never called is allowed and marks it
+ * loaded; exporting from one is QC_EINVAL (there is nothing to save).
+ *   qc_actor / qc_mactor: the prepared weights as the kernels read them (the effective weights' fragments, the
+ *     padded biases; a natural-layout copy does not exist), which layers carry sigma, and the seed. The seed is
+ *     taken from the blob, not compared.
+ *   qc_replay: beta, the sampling counter, the device State (data_pointer, len, passes, max, the two Philox
+ *     counters, the store epoch), the whole tree and the rows. Rows at and past len are left out only while State
+ *     proves them never written (every add so far sequential and len < capacity), else all capacity rows are
+ *     saved: the blob's size depends on the state. The owner tags are not saved (an import zeroes them; a later
+ *     store's tags are above every earlier one's either way).
+ *   qc_learner / qc_mlearner: updates, step, backup_counter, lr (as qc_*_set_lr left it; the create-time lr is
+ *     not compared), l1, l2, the non-finite and out-of-range counters behind qc_*_stats, the parameters, the target
+ *     network's, LaProp's exp_avg, exp_avg_sq and exp_mean_avg, and the prepared fragments of both networks with
+ *     the weight norms, copied as they are. The gradients of the last update (qc_*_grads) are not saved: an
+ *     import zeroes them. */
+int qc_actor_state_bytes(qc_actor* a, uint64_t* n);
+int qc_actor_state_export(qc_actor* a, void* host_dst, uint64_t n);
+int qc_actor_state_import(qc_actor* a, const void* host_src, uint64_t n);
+int qc_mactor_state_bytes(qc_mactor* a, uint64_t* n);
+int qc_mactor_state_export(qc_mactor* a, void* host_dst, uint64_t n);
+int qc_mactor_state_import(qc_mactor* a, const void* host_src, uint64_t n);
+int qc_replay_state_bytes(qc_replay* r, uint64_t* n);
+int qc_replay_state_export(qc_replay* r, void* host_dst, uint64_t n);
+int qc_replay_state_import(qc_replay* r, const void* host_src, uint64_t n);
+int qc_learner_state_bytes(qc_learner* l, uint64_t* n);
+int qc_learner_state_export(qc_learner* l, void* host_dst, uint64_t n);
+int qc_learner_state_import(qc_learner* l, const void* host_src, uint64_t n);
+int qc_mlearner_state_bytes(qc_mlearner* l, uint64_t* n);
+int qc_mlearner_state_export(qc_mlearner* l, void* host_dst, uint64_t n);
+int qc_mlearner_state_import(qc_mlearner* l, const void* host_src, uint64_t n);
+
 /* ---- batched episode loop: the per-control-step bookkeeping of Control.do_episode --------------------------
  * (IHO/main_parallel.py:242-268, IQO/main_parallel.py:190-221; the cartpoles, described first) for every env after a
  * step call of one control interval, on the device (BatchedEnv reset="deferred"): pending[e] (in) marks the envs

@@ -14,8 +14,11 @@ default 65 536: the drivers' 12.6 M rows of 2 006 floats would be 100 GB).
 Prints one JSON line: RL steps/s (decisions), env-steps/s and the actor's / replay's share of the loop.
 With --physics qo --reset warmup the finished envs warm up inside the following calls (BatchedEnv reset='warmup');
 --t-max and --init-time set the episode truncation and the reset's free-evolution time.
+--checkpoint PATH saves env, actor, memory and learner (checkpoint.save) after the timed loop and reports
+checkpoint_save_ms and checkpoint_bytes; --resume PATH loads such a file before the warm-up (checkpoint.load, into
+objects built with the same options) and reports checkpoint_load_ms.
 usage: python tools/bench_loop.py [--batch B] [--steps K] [--input xp|wavefunction|measurements] [--physics iho|iqo|ho|qo]
-       [--reset immediate|deferred|warmup] [--t-max T] [--init-time LO HI]"""
+       [--reset immediate|deferred|warmup] [--t-max T] [--init-time LO HI] [--checkpoint PATH] [--resume PATH]"""
 import argparse
 import json
 import os
@@ -26,6 +29,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import torch  # noqa: E402
 
+from deepreinforcementlearningcontrolofquantumcartpoles_amd import checkpoint  # noqa: E402
 from deepreinforcementlearningcontrolofquantumcartpoles_amd import config as cfg  # noqa: E402
 from deepreinforcementlearningcontrolofquantumcartpoles_amd.actor import (  # noqa: E402
     DQNActor, MeasurementActor, random_direct_dqn, random_dqn_measurement)
@@ -58,6 +62,10 @@ def main():
     ap.add_argument("--learn", type=int, default=0,
                     help="device learner steps (DQNLearner.step / MeasurementLearner.step: sample(512) -> update -> "
                          "batch_update) plus one weight push into the actor per control step; 0: none (the default)")
+    ap.add_argument("--checkpoint", metavar="PATH", default=None,
+                    help="save env, actor, memory and learner after the timed loop (checkpoint.save)")
+    ap.add_argument("--resume", metavar="PATH", default=None,
+                    help="load a --checkpoint file of a run with the same options before the warm-up")
     args = ap.parse_args()
     if args.reset is None:
         args.reset = "deferred" if args.input == "xp" else "immediate"
@@ -97,8 +105,19 @@ def main():
     elif args.learn:
         from deepreinforcementlearningcontrolofquantumcartpoles_amd.learner import DQNLearner
         learner = DQNLearner(wnet if wave else random_direct_dqn(seed=1), batch_size=512, device=0, seed=4)
-    obs = env.reset()
-    steps_done = 0
+    objects = {"env": env, "actor": actor, "memory": mem}
+    if learner is not None:
+        objects["learner"] = learner
+    extra = {}
+    if args.resume:
+        torch.cuda.synchronize()
+        tl = time.perf_counter()
+        saved = checkpoint.load(args.resume, objects)
+        extra["checkpoint_load_ms"] = (time.perf_counter() - tl) * 1e3
+        obs, steps_done = env.obs, int(saved["steps_done"])
+    else:
+        obs = env.reset()
+        steps_done = 0
     ev = lambda: torch.cuda.Event(enable_timing=True)   # noqa: E731
     marks = []                                          # (actor start, end, replay start, end) per timed step
     rows = torch.zeros((), dtype=torch.int64, device="cuda")
@@ -154,7 +173,11 @@ def main():
     K = args.steps
     net = "DQN_measurement" if meas else "direct_DQN"
     what = f"{args.physics.upper()} driver defaults" if wave else "IHO N=512"
-    extra = {}
+    if args.checkpoint:
+        ts = time.perf_counter()
+        checkpoint.save(args.checkpoint, objects, extra={"steps_done": steps_done})
+        extra["checkpoint_save_ms"] = (time.perf_counter() - ts) * 1e3
+        extra["checkpoint_bytes"] = os.path.getsize(args.checkpoint)
     if args.reset == "warmup":   # share of the batch in its free evolution (not controlled) per call
         extra["warming_fraction_per_control_step"] = int(n_warming) / (B * K)
     if args.t_max is not None:
