@@ -48,7 +48,10 @@ EXPORTS = (
     "qc_mlearner_create", "qc_mlearner_destroy", "qc_mlearner_last_error", "qc_mlearner_set_stream",
     "qc_mlearner_noise_len", "qc_mlearner_load", "qc_mlearner_layers", "qc_mlearner_update", "qc_mlearner_set_lr",
     "qc_mlearner_stats", "qc_mlearner_grads", "qc_mlearner_apply", "qc_mlearner_states",
-) + tuple(f"qc_{kind}_state_{op}" for kind in ("actor", "mactor", "replay", "learner", "mlearner")
+    "qc_learner_set_backup_period", "qc_mlearner_set_backup_period",
+    "qc_sched_create", "qc_sched_destroy", "qc_sched_last_error", "qc_sched_set_stream", "qc_sched_tick",
+    "qc_sched_poll", "qc_sched_seek",
+) + tuple(f"qc_{kind}_state_{op}" for kind in ("actor", "mactor", "replay", "learner", "mlearner", "sched")
           for op in ("bytes", "export", "import"))   # checkpoint: a handle's whole state as one host buffer
 
 
@@ -201,6 +204,66 @@ class QcLearnerStats(ctypes.Structure):
         ("lr", ctypes.c_double),
         ("backup_counter", ctypes.c_int32),
         ("launches_per_update", ctypes.c_int32),
+    ]
+
+
+QC_SCHED_CARTPOLE, QC_SCHED_COOLING = 0, 1
+QC_SCHED_MAX_LR_STEPS, QC_SCHED_MAX_RUNGS = 8, 4
+QC_SCHED_ERR_OVERRUN = 1
+
+
+class QcSchedParams(ctypes.Structure):
+    _fields_ = [
+        ("rule", ctypes.c_int32),
+        ("train", ctypes.c_int32),
+        ("start_time", ctypes.c_double),
+        ("fall_time", ctypes.c_double),
+        ("t_full", ctypes.c_double),
+        ("first_interval_time", ctypes.c_double),
+        ("fail_limit", ctypes.c_int32),
+        ("batch_size", ctypes.c_int32),
+        ("n_times_per_sample", ctypes.c_double),
+        ("max_updates_per_tick", ctypes.c_int64),
+        ("min_rows", ctypes.c_int64),
+        ("num_episodes", ctypes.c_int64),
+        ("give_up_episodes", ctypes.c_int64),
+        ("lr_init", ctypes.c_double),
+        ("lr_cap", ctypes.c_double),
+        ("n_lr_steps", ctypes.c_int32),
+        ("n_rungs", ctypes.c_int32),
+        ("lr_episode", ctypes.c_int64 * QC_SCHED_MAX_LR_STEPS),
+        ("lr_value", ctypes.c_double * QC_SCHED_MAX_LR_STEPS),
+        ("backup_period", ctypes.c_int32),
+        ("warm_backup_period", ctypes.c_int32),
+        ("save_interval", ctypes.c_int64),
+        ("actor_update_time", ctypes.c_double),
+        ("rung_achieved", ctypes.c_double * QC_SCHED_MAX_RUNGS),
+        ("rung_below", ctypes.c_double * QC_SCHED_MAX_RUNGS),
+        ("rung_time", ctypes.c_double * QC_SCHED_MAX_RUNGS),
+    ]
+
+
+class QcSchedSnapshot(ctypes.Structure):
+    _fields_ = [
+        ("tick", ctypes.c_int64),
+        ("n_updates", ctypes.c_int64),
+        ("push", ctypes.c_int32),
+        ("save", ctypes.c_int32),
+        ("stop", ctypes.c_int32),
+        ("learning", ctypes.c_int32),
+        ("lr", ctypes.c_double),
+        ("backup_period", ctypes.c_int64),
+        ("episode", ctypes.c_int64),
+        ("last_achieved", ctypes.c_double),
+        ("t_done", ctypes.c_double),
+        ("pending", ctypes.c_double),
+        ("actor_update_time", ctypes.c_double),
+        ("total_episodes", ctypes.c_int64),
+        ("total_rows", ctypes.c_int64),
+        ("error", ctypes.c_int64),
+        ("mean", ctypes.c_double),
+        ("sem", ctypes.c_double),
+        ("n", ctypes.c_int64),
     ]
 
 
@@ -377,11 +440,22 @@ def lib() -> ctypes.CDLL:
     L.qc_mlearner_layers.argtypes = [vp, ctypes.c_int, P(QcDqnLayer)]
     L.qc_mlearner_update.argtypes = [vp, vp, vp, vp, u64, vp, vp]
     L.qc_mlearner_set_lr.argtypes = [vp, d]
+    L.qc_learner_set_backup_period.argtypes = [vp, i32]
+    L.qc_mlearner_set_backup_period.argtypes = [vp, i32]
+    L.qc_sched_create.argtypes = [P(QcSchedParams), ctypes.c_int, P(vp)]
+    L.qc_sched_destroy.argtypes = [vp]
+    L.qc_sched_destroy.restype = None
+    L.qc_sched_last_error.argtypes = [vp]
+    L.qc_sched_last_error.restype = ctypes.c_char_p
+    L.qc_sched_set_stream.argtypes = [vp, vp]
+    L.qc_sched_tick.argtypes = [vp, vp, i64, vp, vp, i64]
+    L.qc_sched_poll.argtypes = [vp, i64, P(QcSchedSnapshot)]
+    L.qc_sched_seek.argtypes = [vp, vp]
     L.qc_mlearner_stats.argtypes = [vp, P(QcLearnerStats)]
     L.qc_mlearner_grads.argtypes = [vp, P(QcDqnLayer)]
     L.qc_mlearner_apply.argtypes = [vp, P(QcDqnLayer)]
     L.qc_mlearner_states.argtypes = [vp, vp, vp, vp]
-    for kind in ("actor", "mactor", "replay", "learner", "mlearner"):
+    for kind in ("actor", "mactor", "replay", "learner", "mlearner", "sched"):
         getattr(L, f"qc_{kind}_state_bytes").argtypes = [vp, P(u64)]
         getattr(L, f"qc_{kind}_state_export").argtypes = [vp, vp, u64]
         getattr(L, f"qc_{kind}_state_import").argtypes = [vp, vp, u64]
@@ -429,6 +503,7 @@ check_mactor = _checker("qc_mactor")
 check_learner = _checker("qc_learner")
 check_mlearner = _checker("qc_mlearner")
 check_replay = _checker("qc_replay")
+check_sched = _checker("qc_sched")
 
 
 class DeviceHandle:

@@ -680,6 +680,13 @@ int set_lr(LearnerCore& c, double lr) {
     return QC_OK;
 }
 
+int set_backup_period(LearnerCore& c, int period) {
+    if (period < 1) { c.err = "backup_period must be >= 1"; return QC_EINVAL; }
+    c.backup_period = period;
+    c.backup_counter %= period;
+    return QC_OK;
+}
+
 namespace {
 // the layers' tensors -> dst (the parameters or the gradients), device to device on the stream; stops at a missing
 // tensor with hipErrorInvalidValue
@@ -839,7 +846,8 @@ namespace {
 struct StateHead {
     int64_t updates, step;
     double lr, l1, l2;
-    int32_t backup_counter, pad;
+    int32_t backup_counter;
+    int32_t backup_period_set;   // the period in use where set_backup_period changed it, else 0 (as every earlier blob)
     int32_t cnt[2];   // d_cnt: non-finite losses, the out-of-range-action flag
 };
 struct StatePart {
@@ -869,7 +877,7 @@ uint64_t state_payload(const LearnerCore& c) {
 void put_core_fields(const LearnerCore& c, state::Header& h) {
     state::put_i(h, "n_actions", c.A);
     state::put_i(h, "batch_size", c.B);
-    state::put_i(h, "backup_period", c.backup_period);
+    state::put_i(h, "backup_period", c.backup_period0);
     state::put_i(h, "target_mode", c.target_mode);
     state::put_f(h, "gamma", c.gamma);
     state::put_f(h, "alive_reward", c.alive_reward);
@@ -906,6 +914,7 @@ int state_export_core(LearnerCore& c, state::Header h, void* host_dst, uint64_t 
     s.updates = c.updates; s.step = c.step;
     s.lr = c.lr; s.l1 = c.l1; s.l2 = c.l2;
     s.backup_counter = c.backup_counter;
+    s.backup_period_set = c.backup_period != c.backup_period0 ? c.backup_period : 0;
     hipError_t e = hipStreamSynchronize(c.stream);
     if (e == hipSuccess) e = hipMemcpy(s.cnt, c.d_cnt, sizeof(s.cnt), hipMemcpyDeviceToHost);
     std::memcpy(host_dst, &h, sizeof(h));
@@ -931,9 +940,12 @@ int state_import_core(LearnerCore& c, const state::Header& mine, const void* hos
     if (bad.empty()) {
         std::memcpy(&s, (const unsigned char*)host_src + sizeof(state::Header), sizeof(s));
         const std::string who = std::string(c.name) + "_state_import: ";
-        if (s.backup_counter < 0 || s.backup_counter >= c.backup_period)
+        const int period = s.backup_period_set > 0 ? s.backup_period_set : c.backup_period0;
+        if (s.backup_period_set < 0)
+            bad = who + "backup_period in use: blob " + std::to_string(s.backup_period_set) + ", expected >= 0";
+        else if (s.backup_counter < 0 || s.backup_counter >= period)
             bad = who + "backup_counter: blob " + std::to_string(s.backup_counter) + ", handle's backup_period " +
-                  std::to_string(c.backup_period);
+                  std::to_string(period);
         else if (s.step < 0 || s.updates < 0)
             bad = who + "step / updates: blob " + std::to_string(s.step) + " / " + std::to_string(s.updates) +
                   ", expected >= 0";
@@ -962,6 +974,7 @@ int state_import_core(LearnerCore& c, const state::Header& mine, const void* hos
     c.updates = s.updates; c.step = s.step;
     c.lr = s.lr; c.l1 = s.l1; c.l2 = s.l2;
     c.backup_counter = s.backup_counter;
+    c.backup_period = s.backup_period_set > 0 ? s.backup_period_set : c.backup_period0;
     c.loaded = true;
     return QC_OK;
 }
@@ -1096,6 +1109,7 @@ int qc_learner_grads(qc_learner* l, qc_dqn_layer out[6]) {
 }
 
 int qc_learner_set_lr(qc_learner* l, double lr) { return l ? set_lr(*l, lr) : QC_EINVAL; }
+int qc_learner_set_backup_period(qc_learner* l, int32_t period) { return l ? set_backup_period(*l, period) : QC_EINVAL; }
 
 int qc_learner_update(qc_learner* l, const float* transitions, const float* is_weights, const float* noise,
                       uint64_t counter, float* unweighted_loss, float* loss) {

@@ -133,6 +133,7 @@ struct LearnerCore {
     int A = 0, B = 0, noise_len = 0;
     // what an update needs from the handle's params
     int backup_period = 1, target_mode = QC_TD_ALIVE;
+    int backup_period0 = 1;   // the create-time period: what the state header carries (set_backup_period changes backup_period)
     double gamma = 0, alive_reward = 0, failing_reward = 0;
     uint64_t seed = 0;
     double b1 = 0, b2 = 0;    // LaProp's betas
@@ -175,7 +176,7 @@ void take_params(LearnerCore& c, const char* name, const Params& p, int device, 
     c.name = name;
     c.device = device;
     c.A = p.n_actions; c.B = p.batch_size; c.noise_len = noise_len;
-    c.backup_period = p.backup_period; c.target_mode = p.target_mode;
+    c.backup_period = c.backup_period0 = p.backup_period; c.target_mode = p.target_mode;
     c.gamma = p.gamma; c.alive_reward = p.alive_reward; c.failing_reward = p.failing_reward;
     c.seed = p.seed;
     c.lr = p.lr;
@@ -221,6 +222,9 @@ void destroy_core(LearnerCore& c);
 // the layers' tensors inside one flat buffer (the parameters, the target's, or the gradients)
 void layer_views(const LearnerCore& c, const float* base, qc_dqn_layer* out);
 int set_lr(LearnerCore& c, double lr);
+// the target network's period from the next update on (Main_System's temporary 100, IHO main_parallel.py:480-481,
+// 546-547); backup_counter is reduced modulo the new period
+int set_backup_period(LearnerCore& c, int period);
 // qc_*_load after the layers' validation: copies, zeroed optimizer state, k_learner_prep, schedule reset
 int load_core(LearnerCore& c, const qc_dqn_layer* layers);
 // qc_*_update's head: the refusals, the target sync at backup_counter == 0, the noise launch; and its end after n launches
@@ -237,7 +241,7 @@ int apply_core(LearnerCore& c, const qc_dqn_layer* grads);
 int stats_core(LearnerCore& c, qc_learner_stats_t* out);
 
 // ---- qc_*_state_bytes / _export / _import of both learners (the blob's header: qcart_state.hpp). The payload is
-// the host schedule (updates, step, backup_counter, lr, l1, l2), the device counters behind qc_*_stats, then P, PT,
+// the host schedule (updates, step, backup_counter, the period set_backup_period left or 0, lr, l1, l2), the device counters behind qc_*_stats, then P, PT,
 // E, V, MU, F, FT and d_norm as they are. The handle passes its own header: its geometry fields first;
 // put_core_fields appends what both params structs share and the buffer sizes
 void put_core_fields(const LearnerCore& c, state::Header& h);

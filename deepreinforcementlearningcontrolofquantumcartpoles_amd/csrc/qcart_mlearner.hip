@@ -577,6 +577,7 @@ int qc_mlearner_grads(qc_mlearner* l, qc_dqn_layer out[8]) {
 }
 
 int qc_mlearner_set_lr(qc_mlearner* l, double lr) { return l ? set_lr(*l, lr) : QC_EINVAL; }
+int qc_mlearner_set_backup_period(qc_mlearner* l, int32_t period) { return l ? set_backup_period(*l, period) : QC_EINVAL; }
 
 int qc_mlearner_states(qc_mlearner* l, const float* transitions, float* next_out, float* prev_out) {
     if (!l || !transitions || !next_out || !prev_out) return QC_EINVAL;

@@ -174,6 +174,12 @@ class BatchedEnv:
             self._fin_read = n
         return self._fin_host
 
+    def finished_ring(self):
+        """(fin, fin_cap, fin_n): the device ring of finished episodes as qc_env_tail writes it, fin [2, fin_cap + 1]
+        float64 (returns, lengths; entry i at column i % fin_cap) and fin_n, the int64 device scalar of episodes
+        appended so far. No copy and no synchronisation: a device consumer (train.Schedule) reads it in stream order."""
+        return self._fin, self._fin_cap, self._fin_n
+
     def _push_finished(self, done: torch.Tensor, ret: torch.Tensor, length: torch.Tensor):
         """Append the finished episodes (env order) to the device ring, no host sync."""
         pos = self._fin_n + torch.cumsum(done, 0) - 1

@@ -136,6 +136,12 @@ class _Learner(L.DeviceHandle):
     def set_lr(self, lr: float):
         self._check(self._fn("set_lr")(self._h, float(lr)))
 
+    def set_backup_period(self, n: int):
+        """The target network's period from the next update on (Main_System's temporary 100 before learning starts,
+        IHO/main_parallel.py:480-481, 546-547); backup_counter is reduced modulo n. A train_state keeps echoing the
+        create-time period and carries the one in use in its blob."""
+        self._check(self._fn("set_backup_period")(self._h, int(n)))
+
     def _rows(self, transitions: torch.Tensor) -> torch.Tensor:
         if transitions.dim() != 2 or tuple(transitions.shape) != (self.batch_size, self.row_len):
             raise ValueError(f"transitions must be [{self.batch_size}, {self.row_len}]")

@@ -499,6 +499,11 @@ int qc_learner_layers(qc_learner* l, int target, qc_dqn_layer out[6]);
 int qc_learner_update(qc_learner* l, const float* transitions, const float* is_weights, const float* noise,
                       uint64_t counter, float* unweighted_loss, float* loss);
 int qc_learner_set_lr(qc_learner* l, double lr);
+/* the target network's period from the next update on (Main_System's temporary 100 before learning starts,
+ * IHO/main_parallel.py:480-481, 546-547); backup_counter is reduced modulo the new period. The state header keeps
+ * the create-time value; the period in use travels in the payload. A learner on which this is never called
+ * behaves, and exports, exactly as before. */
+int qc_learner_set_backup_period(qc_learner* l, int32_t period);
 /* synchronises the stream; QC_EINVAL (once, message via qc_learner_last_error) if an update since the last
  * call saw an out-of-range action, with *out filled either way */
 int qc_learner_stats(qc_learner* l, qc_learner_stats_t* out);
@@ -552,6 +557,7 @@ int qc_mlearner_layers(qc_mlearner* l, int target, qc_dqn_layer out[8]);
 int qc_mlearner_update(qc_mlearner* l, const float* transitions, const float* is_weights, const float* noise,
                        uint64_t counter, float* unweighted_loss, float* loss);
 int qc_mlearner_set_lr(qc_mlearner* l, double lr);
+int qc_mlearner_set_backup_period(qc_mlearner* l, int32_t period);   /* as qc_learner_set_backup_period */
 int qc_mlearner_stats(qc_mlearner* l, qc_learner_stats_t* out);   /* as qc_learner_stats */
 int qc_mlearner_grads(qc_mlearner* l, qc_dqn_layer out[8]);
 int qc_mlearner_apply(qc_mlearner* l, const qc_dqn_layer grads[8]);
@@ -685,6 +691,89 @@ typedef struct qc_env_tail_args {
 } qc_env_tail_args;
 int qc_env_tail(qc_handle* h, const qc_env_tail_args* a);
 int qc_env_warmup_draw(qc_handle* h, const qc_env_tail_args* a, const uint8_t* mask);
+
+/* ---- training schedule: what the drivers decide from the stream of finished episodes ----------------------
+ * The loader loop of each driver's RL.py (IHO:497-535, IQO:495-533, HO:491-538, QO:477-527) and one pass of
+ * Main_System.__call__ with adjust_learning_rate, scale_up_actor_update_time and receive_net's save count
+ * (IHO/main_parallel.py:369-405, 482-559), as one single-workgroup launch per control step that reads the
+ * finished-episode ring qc_env_tail appends to. The host never reads the ring: each tick copies one snapshot into a
+ * pinned slot of its own and records an event; qc_sched_poll waits on that event alone. A tick:
+ *   1. rows = the number of set bytes in valid[0, B); total_rows += rows; pending += rows * 8 / 256 (rows are
+ *      credited in the call that stores them; the reference credits them when their episode ends);
+ *   2. the ring entries [read, *fin_n) in ring order, each through the rule's loader-loop body: episode += 1,
+ *      t_done += t, the rule. If more than fin_cap entries are new the ring was overrun: the sticky error word is
+ *      raised and the walk starts at the oldest entry still present;
+ *   3. one Main_System pass: the updates due (at most max_updates_per_tick, the rest stays pending), the actor push,
+ *      the learning rate and the target period, the save flag, the stop rule;
+ *   4. with train == 0, count / sum / sum of squares of the episode times (mean, sem, n of the snapshot).
+ * Every arithmetic operation is rounded once (no fused multiply-add), in the order csrc/qcart_sched.hpp writes
+ * them, so a host restatement gives the same bits. */
+enum { QC_SCHED_CARTPOLE = 0, QC_SCHED_COOLING = 1 };
+#define QC_SCHED_MAX_LR_STEPS 8
+#define QC_SCHED_MAX_RUNGS 4
+typedef struct qc_sched_params {
+    int32_t rule;                  /* QC_SCHED_*                                                          */
+    int32_t train;                 /* 0: the --test / --LQG accounting: learning in progress is set at the   */
+                                   /* first episode, the rule is not run; no updates, pushes or saves     */
+    double start_time, fall_time;  /* cartpole: the EMA of the episode time starts learning at >= start_time */
+                                   /* and clears it at < fall_time (IHO 20 / 5, IQO 12 / 4)               */
+    double t_full;                 /* cooling: an episode counts as t == t_max iff t >= t_full (the env's    */
+                                   /* t_trunc, t_max - 0.01 dt)                                           */
+    double first_interval_time;    /* cooling: an episode stored no row iff t <= 1.5 first_interval_time     */
+                                   /* (HO/RL.py:499 sets learning in progress on one); 0: no such rule    */
+    int32_t fail_limit;            /* cooling: successive failures that clear learning (HO 10, QO 40)     */
+    int32_t batch_size;
+    double n_times_per_sample;     /* an update is due per D = (8 / n_times_per_sample) (batch_size / 256) pending */
+    int64_t max_updates_per_tick;  /* >= 1                                                                */
+    int64_t min_rows;              /* no update is due while total_rows < min_rows                        */
+    int64_t num_episodes, give_up_episodes;
+    double lr_init;
+    double lr_cap;                 /* lr = min(lr_cap, lr) when learning is first in progress (4e-4; QO 1e-3) */
+    int32_t n_lr_steps, n_rungs;
+    int64_t lr_episode[QC_SCHED_MAX_LR_STEPS];   /* strictly increasing                                   */
+    double lr_value[QC_SCHED_MAX_LR_STEPS];
+    int32_t backup_period, warm_backup_period;   /* the emitted period is warm_backup_period (100) until   */
+                                                 /* learning is first in progress                         */
+    int64_t save_interval;
+    double actor_update_time;      /* its initial value (10)                                              */
+    /* scale_up_actor_update_time's rungs in the order it tests them: the first with last_achieved >           */
+    /* rung_achieved[i] and actor_update_time <= rung_below[i] sets actor_update_time = rung_time[i]      */
+    double rung_achieved[QC_SCHED_MAX_RUNGS], rung_below[QC_SCHED_MAX_RUNGS], rung_time[QC_SCHED_MAX_RUNGS];
+} qc_sched_params;
+typedef struct qc_sched_snapshot {
+    int64_t tick;                  /* 0 for the first qc_sched_tick                                       */
+    int64_t n_updates;
+    int32_t push, save, stop, learning;
+    double lr;
+    int64_t backup_period;
+    int64_t episode;
+    double last_achieved, t_done, pending, actor_update_time;
+    int64_t total_episodes, total_rows;
+    int64_t error;                 /* sticky; bit 0: the ring was overrun                                 */
+    double mean, sem;              /* train == 0: of the episode times so far (sem 0 below two)           */
+    int64_t n;
+} qc_sched_snapshot;
+typedef struct qc_sched qc_sched;
+int qc_sched_create(const qc_sched_params* p, int device, qc_sched** out);
+void qc_sched_destroy(qc_sched* s);
+const char* qc_sched_last_error(const qc_sched* s);
+int qc_sched_set_stream(qc_sched* s, void* stream);
+/* asynchronous: one launch, one copy of the snapshot into the tick's pinned slot, one event record. All pointers
+ * are device pointers: fin [2][fin_cap + 1] and fin_n as qc_env_tail_args has them (the length row is read),
+ * valid [B] (NULL with B == 0: no rows). The first tick has index 0. */
+int qc_sched_tick(qc_sched* s, const double* fin, int64_t fin_cap, const int64_t* fin_n, const uint8_t* valid,
+                  int64_t B);
+/* asynchronous, one small launch: the walk starts at the ring's present end, *fin_n (a device pointer): entries
+ * appended before are not this schedule's (an evaluation on an env that has already run) */
+int qc_sched_seek(qc_sched* s, const int64_t* fin_n);
+/* waits on the event of that tick only (never a device or stream synchronisation) and copies its snapshot out;
+ * the last two ticks are kept, any other is QC_EINVAL */
+int qc_sched_poll(qc_sched* s, int64_t tick, qc_sched_snapshot* out);
+/* as the other kinds' (above): the header fields are the create-time params (the lr schedule and the rungs as
+ * their lengths and a hash of their values), the payload the device state and the tick count */
+int qc_sched_state_bytes(qc_sched* s, uint64_t* n);
+int qc_sched_state_export(qc_sched* s, void* host_dst, uint64_t n);
+int qc_sched_state_import(qc_sched* s, const void* host_src, uint64_t n);
 
 /* ---- step server: the reference's process model on one GPU ------------------------------------------------
  * The drivers run 30-40 actor processes, each with its own `simulation` module stepping ONE env per call
