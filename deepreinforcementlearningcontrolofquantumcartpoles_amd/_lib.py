@@ -51,7 +51,9 @@ EXPORTS = (
     "qc_learner_set_backup_period", "qc_mlearner_set_backup_period",
     "qc_sched_create", "qc_sched_destroy", "qc_sched_last_error", "qc_sched_set_stream", "qc_sched_tick",
     "qc_sched_poll", "qc_sched_seek",
-) + tuple(f"qc_{kind}_state_{op}" for kind in ("actor", "mactor", "replay", "learner", "mlearner", "sched")
+    "qc_monitor_create", "qc_monitor_destroy", "qc_monitor_last_error", "qc_monitor_set_stream", "qc_monitor_receive",
+    "qc_monitor_poll", "qc_monitor_seek", "qc_monitor_table",
+) + tuple(f"qc_{kind}_state_{op}" for kind in ("actor", "mactor", "replay", "learner", "mlearner", "sched", "monitor")
           for op in ("bytes", "export", "import"))   # checkpoint: a handle's whole state as one host buffer
 
 
@@ -121,6 +123,11 @@ class QcEnvTailArgs(ctypes.Structure):
         ("seed", ctypes.c_uint64),
         ("env_offset", ctypes.c_int64),
         ("reset_out", ctypes.c_void_p),
+        # the cooling kinds' per-episode performance; zero / NULL: none
+        ("perf_sum", ctypes.c_void_p),
+        ("perf_n", ctypes.c_void_p),
+        ("perf", ctypes.c_void_p),
+        ("perf_from", ctypes.c_double),
     ]
 
 
@@ -260,6 +267,37 @@ class QcSchedSnapshot(ctypes.Structure):
         ("actor_update_time", ctypes.c_double),
         ("total_episodes", ctypes.c_int64),
         ("total_rows", ctypes.c_int64),
+        ("error", ctypes.c_int64),
+        ("mean", ctypes.c_double),
+        ("sem", ctypes.c_double),
+        ("n", ctypes.c_int64),
+    ]
+
+
+QC_MONITOR_MAX_SAVES, QC_MONITOR_MAX_WINDOW = 64, 16
+QC_MONITOR_ERR_OVERRUN = 1
+
+
+class QcMonitorParams(ctypes.Structure):
+    _fields_ = [
+        ("train", ctypes.c_int32),
+        ("window", ctypes.c_int32),
+        ("min_count", ctypes.c_int32),
+        ("num_of_saves", ctypes.c_int32),
+        ("min_episodes", ctypes.c_int64),
+        ("initial", ctypes.c_double),
+    ]
+
+
+class QcMonitorSnapshot(ctypes.Structure):
+    _fields_ = [
+        ("call", ctypes.c_int64),
+        ("rank", ctypes.c_int64),
+        ("new_avg", ctypes.c_double),
+        ("count", ctypes.c_int64),
+        ("episode_passed", ctypes.c_int64),
+        ("n_filled", ctypes.c_int64),
+        ("total_episodes", ctypes.c_int64),
         ("error", ctypes.c_int64),
         ("mean", ctypes.c_double),
         ("sem", ctypes.c_double),
@@ -451,11 +489,21 @@ def lib() -> ctypes.CDLL:
     L.qc_sched_tick.argtypes = [vp, vp, i64, vp, vp, i64]
     L.qc_sched_poll.argtypes = [vp, i64, P(QcSchedSnapshot)]
     L.qc_sched_seek.argtypes = [vp, vp]
+    L.qc_monitor_create.argtypes = [P(QcMonitorParams), ctypes.c_int, P(vp)]
+    L.qc_monitor_destroy.argtypes = [vp]
+    L.qc_monitor_destroy.restype = None
+    L.qc_monitor_last_error.argtypes = [vp]
+    L.qc_monitor_last_error.restype = ctypes.c_char_p
+    L.qc_monitor_set_stream.argtypes = [vp, vp]
+    L.qc_monitor_receive.argtypes = [vp, vp, i64, vp]
+    L.qc_monitor_poll.argtypes = [vp, i64, P(QcMonitorSnapshot)]
+    L.qc_monitor_seek.argtypes = [vp, vp]
+    L.qc_monitor_table.argtypes = [vp, vp, vp]
     L.qc_mlearner_stats.argtypes = [vp, P(QcLearnerStats)]
     L.qc_mlearner_grads.argtypes = [vp, P(QcDqnLayer)]
     L.qc_mlearner_apply.argtypes = [vp, P(QcDqnLayer)]
     L.qc_mlearner_states.argtypes = [vp, vp, vp, vp]
-    for kind in ("actor", "mactor", "replay", "learner", "mlearner", "sched"):
+    for kind in ("actor", "mactor", "replay", "learner", "mlearner", "sched", "monitor"):
         getattr(L, f"qc_{kind}_state_bytes").argtypes = [vp, P(u64)]
         getattr(L, f"qc_{kind}_state_export").argtypes = [vp, vp, u64]
         getattr(L, f"qc_{kind}_state_import").argtypes = [vp, vp, u64]
@@ -504,6 +552,7 @@ check_learner = _checker("qc_learner")
 check_mlearner = _checker("qc_mlearner")
 check_replay = _checker("qc_replay")
 check_sched = _checker("qc_sched")
+check_monitor = _checker("qc_monitor")
 
 
 class DeviceHandle:

@@ -1020,7 +1020,20 @@ static EnvTailArgs env_tail_kargs(const qc_env_tail_args& x) {
     a.seed = x.seed;
     a.env_offset = x.env_offset;
     a.reset_out = x.reset_out;
+    a.perf_sum = x.perf_sum;
+    a.perf_n = x.perf_n;
+    a.perf = x.perf;
+    a.perf_from = x.perf_from;
     return a;
+}
+
+// the per-episode performance is the cooling drivers' (HO, QO) and needs its two per-env accumulators
+static const char* perf_refusal(const qc_env_tail_args& x) {
+    if (!x.perf) return nullptr;
+    if (x.kind != QC_HO && x.kind != QC_QO)
+        return "perf is the cooling drivers' per-episode performance (QC_HO, QC_QO): the cartpoles have none";
+    if (!x.perf_sum || !x.perf_n) return "perf needs perf_sum and perf_n";
+    return nullptr;
 }
 
 static bool warmup_state_missing(const qc_env_tail_args& x) {
@@ -1038,6 +1051,7 @@ int qc_env_tail(qc_handle* h, const qc_env_tail_args* in) {
     if (x.kind != QC_IHO && x.kind != QC_IQO && x.kind != QC_HO && x.kind != QC_QO)
         return fail(h, QC_EINVAL, "env tail: unknown kind");
     if (x.kind == QC_IQO && !x.term_step) return fail(h, QC_EINVAL, "env tail: IQO needs term_step");
+    if (const char* why = perf_refusal(x)) return fail(h, QC_EINVAL, (std::string("env tail: ") + why).c_str());
     if (x.kind == QC_HO && x.B > 0 && !x.quantity) return fail(h, QC_EINVAL, "env tail: HO needs quantity");
     if (x.kind == QC_QO && (!x.quantity || !(x.dt > 0) || !(x.init_lo >= 0) || !(x.init_hi >= x.init_lo)))
         return fail(h, QC_EINVAL, "env tail: QO needs quantity (the energy), dt > 0 and 0 <= init_lo <= init_hi");
@@ -1059,6 +1073,7 @@ int qc_env_warmup_draw(qc_handle* h, const qc_env_tail_args* in, const uint8_t* 
     if (warmup_state_missing(x) || !x.t || !x.steps || !x.episode_return || x.interval < 1 || !(x.dt > 0) ||
         !(x.init_lo >= 0) || !(x.init_hi >= x.init_lo))
         return fail(h, QC_EINVAL, "env warm-up draw: missing buffer, interval < 1, dt <= 0 or not 0 <= init_lo <= init_hi");
+    if (const char* why = perf_refusal(x)) return fail(h, QC_EINVAL, (std::string("env warm-up draw: ") + why).c_str());
     const EnvTailArgs a = env_tail_kargs(x);
     DeviceGuard g(h->device);
     return launch_warmup_draw(a, mask, h->stream) ? fail(h, QC_EHIP, "env warm-up draw kernel launch failed") : QC_OK;

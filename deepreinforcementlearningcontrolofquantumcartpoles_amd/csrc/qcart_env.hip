@@ -34,6 +34,12 @@
 //   * redraw (warmup_draw, also behind qc_env_warmup_draw): draw n = draws[e]++ of the env's own Philox stream
 //     (tag kWarmTag) gives k and the evolution time; warm_left = ceil(init_t / dt), budget = min(warm_left,
 //     interval), pending = 1: the caller writes the packet before the next step launch.
+// perf (optional, HO and QO): the episode's performance, the mean of `quantity` over the live, non-terminal control
+// steps whose new episode time is past perf_from (HO:247-248, 274-275, 294-295; QO:221, 231-232). perf_sum / perf_n
+// restart at an episode's start (HO's pending branch, QO's go-live and every draw), a step that ends the episode adds
+// nothing, and a finished episode's performance goes to the ring perf at the position of its (return, length):
+// perf_sum / perf_n when it was truncated (t >= t_trunc) with perf_n > 0, else cutoff. Warming envs touch nothing
+// (qc_env_warmup_draw zeroes both; a redraw inside the tail leaves them to the go-live branch).
 // rec_mode[e] (optional) = 2 for an env pending on entry, else 1: qc_record's per-env mode (fresh history /
 // append) for the 'measurements' input.
 // One workgroup walks the batch in chunks of its 1024 threads, a workgroup scan per chunk placing the finished
@@ -79,6 +85,10 @@ __global__ __launch_bounds__(256) void k_warmup_draw(const EnvTailArgs a, const 
     a.t[e] = 0.0;
     a.steps[e] = 0;
     a.episode_return[e] = 0.0;
+    if (a.perf) {
+        a.perf_sum[e] = 0.0;
+        a.perf_n[e] = 0;
+    }
 }
 
 __global__ __launch_bounds__(kTailThreads) void k_env_tail(const EnvTailArgs a) {
@@ -91,7 +101,7 @@ __global__ __launch_bounds__(kTailThreads) void k_env_tail(const EnvTailArgs a) 
     for (int64_t c0 = 0; c0 < a.B; c0 += kTailThreads) {
         const int64_t e = c0 + t;
         int fin = 0;
-        double f_ret = 0.0, f_len = 0.0;
+        double f_ret = 0.0, f_len = 0.0, f_perf = 0.0;
         if (e < a.B) {
             const bool pend = a.pending[e] != 0;
             const bool fail = a.fail_step[e] > 0;
@@ -103,6 +113,9 @@ __global__ __launch_bounds__(kTailThreads) void k_env_tail(const EnvTailArgs a) 
             bool over;
             double tt, ret;
             float rw;
+            // the performance's accounting (a.perf, cooling kinds): bit 0 an episode starts, bit 1 a live control step
+            int pmode = 0;
+            double pq = 0.0;
             if (a.kind == kFamQO) {   // QO cooling with the rolling warm-up
                 const double q = a.quantity[e];
                 const int32_t wl = a.warm_left[e];
@@ -127,6 +140,7 @@ __global__ __launch_bounds__(kTailThreads) void k_env_tail(const EnvTailArgs a) 
                         tt = 0.0;
                         ret = 0.0;
                         go_live = 1;
+                        pmode = 1;
                     } else {
                         redraw = true;
                     }
@@ -140,10 +154,14 @@ __global__ __launch_bounds__(kTailThreads) void k_env_tail(const EnvTailArgs a) 
                     a.valid[e] = over ? 0 : 1;
                     a.budget[e] = a.interval;
                     redraw = over;
+                    pmode = 2;
+                    pq = q;
                 }
                 a.reset_out[e] = go_live;
             } else if (a.kind == 0) {   // HO cooling
                 const double q = a.quantity[e];
+                pmode = pend ? 3 : 2;   // HO's first control step is a live one (HO:247-248)
+                pq = q;
                 if (pend) {
                     tt = ci_dt;
                     ret = 0.0;
@@ -184,6 +202,17 @@ __global__ __launch_bounds__(kTailThreads) void k_env_tail(const EnvTailArgs a) 
             a.episode_return[e] = ret;
             a.reward[e] = rw;
             a.done[e] = over ? 1 : 0;
+            if (a.perf && pmode) {
+                double ps = (pmode & 1) ? 0.0 : a.perf_sum[e];
+                int64_t pn = (pmode & 1) ? 0 : a.perf_n[e];
+                if ((pmode & 2) && !over && tt > a.perf_from) {   // a terminal step adds nothing (the reference breaks first)
+                    ps = __dadd_rn(ps, pq);
+                    pn += 1;
+                }
+                a.perf_sum[e] = ps;
+                a.perf_n[e] = pn;
+                f_perf = (tt >= a.t_trunc && pn > 0) ? __ddiv_rn(ps, (double)pn) : a.cutoff;
+            }
             if (a.kind == kFamQO) {   // pending: the packet of a new draw is to be written before the next step
                 a.pending[e] = 0;
                 if (redraw) warmup_draw(a, e);
@@ -209,6 +238,7 @@ __global__ __launch_bounds__(kTailThreads) void k_env_tail(const EnvTailArgs a) 
             const int64_t pos = (base + woff + before) % a.fin_cap;
             a.fin[pos] = f_ret;
             a.fin[a.fin_cap + 1 + pos] = f_len;
+            if (a.perf) a.perf[pos] = f_perf;
         }
         __syncthreads();
         if (t == 0) base += tot;

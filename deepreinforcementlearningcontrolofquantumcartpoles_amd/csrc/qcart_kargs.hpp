@@ -211,6 +211,11 @@ struct EnvTailArgs {
     uint64_t seed;
     int64_t env_offset;
     uint8_t* reset_out;
+    // the cooling kinds' per-episode performance (optional: perf NULL leaves all four unread)
+    double* perf_sum;
+    int64_t* perf_n;
+    double* perf;
+    double perf_from;
 };
 int launch_env_tail(const EnvTailArgs& a, void* stream);
 int launch_warmup_draw(const EnvTailArgs& a, const uint8_t* mask, void* stream);   // qc_env_warmup_draw

@@ -18,7 +18,7 @@ constexpr uint32_t kMagic = 0x54534351u;   // "QCST", little endian
 constexpr uint32_t kFormat = 1;            // blob format version; a blob with a newer one is refused
 constexpr int kMaxFields = 24;
 constexpr int kNameLen = 24;
-enum Kind : uint32_t { kActor = 1, kMactor = 2, kReplay = 3, kLearner = 4, kMlearner = 5, kSched = 6 };
+enum Kind : uint32_t { kActor = 1, kMactor = 2, kReplay = 3, kLearner = 4, kMlearner = 5, kSched = 6, kMonitor = 7 };
 enum Type : uint32_t { kI64 = 0, kU64 = 1, kF64 = 2 };
 
 struct Field {
@@ -43,6 +43,7 @@ inline const char* kind_name(uint32_t k) {
         case kLearner: return "qc_learner";
         case kMlearner: return "qc_mlearner";
         case kSched: return "qc_sched";
+        case kMonitor: return "qc_monitor";
         default: return "unknown";
     }
 }

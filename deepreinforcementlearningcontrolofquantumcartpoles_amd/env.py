@@ -55,6 +55,13 @@ intervals, no one-interval reset: it has "immediate" and "warmup"):
     and returns the observation buffer as it is. The draws come from the env's own Philox stream, not
     from the immediate mode's torch generator, and the warm-up runs in control intervals instead of 1440-step
     launches: the scheme is the immediate mode's, the trajectories are not bitwise its.
+
+performance_from (HO and QO, optional): the cooling drivers' per-episode performance, the mean phonon number / energy
+over the control steps whose episode time is past it (HO/main_parallel.py:247-248, 294-295; QO/main_parallel.py:221,
+231-232): a step that ends the episode is not counted, and only an episode truncated at t_max with at least one counted
+step reports its mean, every other one the cutoff. It goes to a ring beside the finished-episode ring, at the same
+position (performance_ring, finished_performances): qc_env_tail keeps it in the deferred and warm-up modes, the
+immediate mode by the same add and divide in torch, so an env's performances are bitwise the same in both.
 """
 from __future__ import annotations
 
@@ -75,7 +82,8 @@ class BatchedEnv:
                  reward_multiply: float = 1.0, t_max: float = 100.0, phonon_cutoff: float = 20.0,
                  energy_cutoff: float = 12.0, init_energy_cutoff: float = 7.5, auto_reset: bool = True,
                  reset_kind: str = "reference", input: str = "xp", read_length: Optional[int] = None,
-                 reset: str = "immediate", init_time: tuple = (15.0, 20.0)):
+                 reset: str = "immediate", init_time: tuple = (15.0, 20.0),
+                 performance_from: Optional[float] = None):
         self.ph = physics
         self.B = int(batch)
         self.st = Stepper(physics, self.B, device, seed=seed, env_offset=env_offset)
@@ -119,6 +127,12 @@ class BatchedEnv:
         if reset == "deferred" and not auto_reset:
             raise ValueError("reset='deferred' is an auto-reset mode (HO, IHO, IQO): it needs auto_reset")
         self.reset_mode = reset
+        # the cooling drivers' per-episode performance: the mean phonon number (HO) / energy (QO) over the control
+        # steps past this episode time (HO:247-248, 294-295; QO:221, 231-232); None: not kept
+        if performance_from is not None and self.cartpole:
+            raise ValueError("performance_from is the cooling drivers' (HO, QO) per-episode performance: the "
+                             "cartpoles (IHO, IQO) are measured by their episode time")
+        self.performance_from = None if performance_from is None else float(performance_from)
         # what a state_dict echoes and load_state_dict compares (the stepper and the record add their own)
         self._made = {"kind": "BatchedEnv", "family": physics.family, "B": self.B, "env_offset": int(env_offset),
                       "input": input, "reset": reset, "reset_kind": reset_kind, "seed": int(seed),
@@ -127,6 +141,8 @@ class BatchedEnv:
                       "t_max": float(t_max), "phonon_cutoff": float(phonon_cutoff),
                       "energy_cutoff": float(energy_cutoff), "init_energy_cutoff": float(init_energy_cutoff),
                       "init_time": self.init_time}
+        if self.performance_from is not None:
+            self._made["performance_from"] = self.performance_from
         self._pending = torch.zeros(self.B, dtype=torch.uint8, device=self.dev)
         self._calls = 0
         self.rec = None
@@ -150,6 +166,14 @@ class BatchedEnv:
         self._fin_n = torch.zeros((), dtype=torch.int64, device=self.dev)
         self._fin_read = 0
         self._fin_host: list = []
+        if self.performance_from is not None:
+            # the running sum and count of the episode, and the finished episodes' performance at the ring
+            # position of their (return, length) (slot _fin_cap: the sink)
+            self._perf_sum = z(torch.float64)
+            self._perf_n = z(torch.int64)
+            self._perf = torch.zeros(self._fin_cap + 1, dtype=torch.float64, device=self.dev)
+            self._perf_read = 0
+            self._perf_host: list = []
         if reset == "warmup":
             # per-env warm-up state, advanced by qc_env_tail (kind QC_QO) and started by qc_env_warmup_draw
             self._seed, self._env_offset = int(seed), int(env_offset)
@@ -180,12 +204,38 @@ class BatchedEnv:
         appended so far. No copy and no synchronisation: a device consumer (train.Schedule) reads it in stream order."""
         return self._fin, self._fin_cap, self._fin_n
 
-    def _push_finished(self, done: torch.Tensor, ret: torch.Tensor, length: torch.Tensor):
+    def performance_ring(self):
+        """(perf, fin_cap, fin_n): the device ring of the finished episodes' performance, perf [fin_cap + 1] float64
+        with entry i at column i % fin_cap, the position of its (return, length) in finished_ring(). No copy and no
+        synchronisation. Needs performance_from."""
+        if self.performance_from is None:
+            raise ValueError("this env keeps no performance: make it with performance_from")
+        return self._perf, self._fin_cap, self._fin_n
+
+    @property
+    def finished_performances(self) -> list:
+        """float64 CPU tensors of the performances of the episodes finished so far, one entry per read that found
+        new ones, with a read position of its own (finished_returns' is not moved). At most the last _fin_cap
+        episodes between two reads are kept. Needs performance_from."""
+        if self.performance_from is None:
+            raise ValueError("this env keeps no performance: make it with performance_from")
+        n = int(self._fin_n)
+        if n > self._perf_read:
+            lo = max(self._perf_read, n - self._fin_cap)
+            idx = torch.arange(lo, n, device=self.dev) % self._fin_cap
+            self._perf_host.append(self._perf[idx].cpu())
+            self._perf_read = n
+        return self._perf_host
+
+    def _push_finished(self, done: torch.Tensor, ret: torch.Tensor, length: torch.Tensor,
+                       perf: Optional[torch.Tensor] = None):
         """Append the finished episodes (env order) to the device ring, no host sync."""
         pos = self._fin_n + torch.cumsum(done, 0) - 1
         slot = torch.where(done, pos % self._fin_cap, torch.full_like(pos, self._fin_cap))
         self._fin[0].index_copy_(0, slot, ret)   # duplicates only into the sink
         self._fin[1].index_copy_(0, slot, length)
+        if perf is not None:
+            self._perf.index_copy_(0, slot, perf)
         self._fin_n += done.sum()
 
     # ------------------------------------------------------------------ observation
@@ -262,6 +312,11 @@ class BatchedEnv:
         self.steps = torch.where(mask, torch.zeros_like(self.steps), self.steps)
         self.episode_return = torch.where(mask, torch.zeros_like(self.episode_return), self.episode_return)
         self.last_action = torch.where(mask, torch.full_like(self.last_action, self.half), self.last_action)
+        keep_perf = self.performance_from is not None
+        if keep_perf:   # a new episode's performance starts from nothing
+            self._perf_sum = torch.where(mask, torch.zeros_like(self._perf_sum), self._perf_sum)
+            self._perf_n = torch.where(mask, torch.zeros_like(self._perf_n), self._perf_n)
+        first_q = None
         if self.first_interval:
             # no control at the zero-th step: one zero-force interval first (IHO:242-268, IQO:190-221,
             # HO:237-257). An episode that already ends at i = control_interval stores no transition
@@ -281,15 +336,25 @@ class BatchedEnv:
                 elif fam == cfg.IHO:
                     bad |= out["obs"][:, 0].abs() > self.ph.xth
                 else:   # HO: phonon > cutoff at the first control step ends the episode (HO:240-246)
-                    bad |= self.st.phonon_number(self.psi) > self.phonon_cutoff
+                    # (every pass steps only the envs it redoes, so the last pass's value is every masked env's
+                    # phonon number after its own first interval)
+                    first_q = self.st.phonon_number(self.psi)
+                    bad |= first_q > self.phonon_cutoff
                 bad &= todo
                 if bool(bad.any()):
                     length = torch.where(mask, self.t + self.ci * self.ph.dt, self.t)
-                    self._push_finished(bad, torch.zeros_like(self.t), length)
+                    # (nothing was counted yet: such an episode's performance is the cutoff)
+                    self._push_finished(bad, torch.zeros_like(self.t), length,
+                                        torch.full_like(self.t, self.phonon_cutoff) if keep_perf else None)
                     self._reset_states(bad)
                 todo = bad
             self.t = torch.where(mask, self.t + self.ci * self.ph.dt, self.t)
             self.steps = torch.where(mask, self.steps + self.ci, self.steps)
+            if keep_perf and first_q is not None:
+                # HO's first control step is a live one (HO:247-248): it counts when it is past performance_from
+                acc = mask & (self.t > self.performance_from)
+                self._perf_sum = torch.where(acc, self._perf_sum + first_q, self._perf_sum)
+                self._perf_n = self._perf_n + acc
         if self.rec is not None:
             self.obs = self.rec.hist
             return self.obs
@@ -326,7 +391,8 @@ class BatchedEnv:
                             fin_cap=self._fin_cap, fin_n=p(self._fin_n), quantity=p(quantity),
                             cutoff=self.phonon_cutoff if cooling else 0.0,
                             t_trunc=self.t_max - 0.01 * self.ph.dt if cooling else 0.0,
-                            reward_multiply=self.reward_multiply if cooling else 0.0, rec_mode=p(rec_mode))
+                            reward_multiply=self.reward_multiply if cooling else 0.0, rec_mode=p(rec_mode),
+                            **self._perf_args())
         self.st._bind_stream()
         L.check(L.lib().qc_env_tail(self.st._h, ctypes.byref(a)), self.st._h)
         valid_b = valid.view(torch.bool)
@@ -351,6 +417,13 @@ class BatchedEnv:
                      "numerical_failure": done_b & (out["fail_step"] > 0)})
         return obs, reward, done_b, info
 
+    def _perf_args(self) -> dict:
+        """qc_env_tail_args' performance fields (none without performance_from)."""
+        if self.performance_from is None:
+            return {}
+        return dict(perf_sum=self._perf_sum.data_ptr(), perf_n=self._perf_n.data_ptr(), perf=self._perf.data_ptr(),
+                    perf_from=self.performance_from)
+
     def _warmup_args(self, **kw):
         """qc_env_tail_args of the warm-up mode: the per-env state and the draw parameters (kw: the per-call fields)."""
         p = lambda t: t.data_ptr()   # noqa: E731
@@ -361,7 +434,7 @@ class BatchedEnv:
             cutoff=self.energy_cutoff, t_trunc=self.t_max - 0.01 * self.ph.dt, reward_multiply=self.reward_multiply,
             warm_left=p(self._warm_left), warm_fail=p(self._warm_fail), draws=p(self._draws), k=p(self._k),
             budget=p(self._budget), init_energy_cutoff=self.init_energy_cutoff, init_lo=self.init_time[0],
-            init_hi=self.init_time[1], seed=self._seed, env_offset=self._env_offset, **kw)
+            init_hi=self.init_time[1], seed=self._seed, env_offset=self._env_offset, **self._perf_args(), **kw)
 
     def _step_warmup(self, actions: torch.Tensor):
         """reset='warmup' (QO): the packets of the new draws, one step launch with per-env budgets (a warming env at
@@ -435,6 +508,14 @@ class BatchedEnv:
             reward = -q * self.reward_multiply
             valid = ~done
             numerical = fail
+            if self.performance_from is not None:
+                # one add and one divide under qc_env_tail's conditions: a terminal step adds nothing, and only a
+                # truncated episode that counted something reports its mean, every other one the cutoff
+                acc = valid & (self.t > self.performance_from)
+                self._perf_sum = torch.where(acc, self._perf_sum + q, self._perf_sum)
+                self._perf_n = self._perf_n + acc
+                perf = torch.where(truncated & (self._perf_n > 0), self._perf_sum / self._perf_n.to(torch.float64),
+                                   torch.full_like(q, cutoff))
         self.episode_return = self.episode_return + torch.where(valid, reward, torch.zeros_like(reward))
         info = {"valid": valid, "numerical_failure": numerical & done, "t": self.t.clone(),
                 "last_obs": last_obs if self.rec is None else None, "fail_step": out["fail_step"]}
@@ -451,7 +532,11 @@ class BatchedEnv:
                 info["terminal_obs"] = obs.clone()
             info["episode_return"] = self.episode_return.clone()
             info["episode_length"] = self.t.clone()
-            self._push_finished(done, self.episode_return, self.t)
+            if self.performance_from is not None:
+                info["episode_performance"] = perf.clone()
+                self._push_finished(done, self.episode_return, self.t, perf)
+            else:
+                self._push_finished(done, self.episode_return, self.t)
             if self.auto_reset:
                 self.reset(done)
         return self.obs, reward.to(torch.float32), done, info
@@ -467,6 +552,8 @@ class BatchedEnv:
             names.append("rows")
         if self.reset_mode == "warmup":
             names += self._WARM
+        if self.performance_from is not None:
+            names += ["_perf_sum", "_perf_n", "_perf"]
         return names
 
     def _made_for(self) -> dict:
@@ -483,6 +570,8 @@ class BatchedEnv:
         for name in self._state_tensors():
             st[name] = getattr(self, name).cpu()
         st["_fin_read"] = int(self._fin_read)
+        if self.performance_from is not None:
+            st["_perf_read"] = int(self._perf_read)
         st["_calls"] = int(self._calls)
         st["generator"] = self.gen.get_state().cpu()
         st["record"] = self.rec.state_dict() if self.rec is not None else None
@@ -494,8 +583,13 @@ class BatchedEnv:
         env_offset, input, reset mode, reset_kind, read_length, seed, the episode rules), or a tensor of another
         shape. Changes nothing."""
         names = self._state_tensors()
+        keep_perf = self.performance_from is not None
+        if not keep_perf and isinstance(state, dict) and "performance_from" in state:
+            raise ValueError(f"BatchedEnv: performance_from differs: the state was made for "
+                             f"{state['performance_from']!r}, this object for None")
         L.check_echo("BatchedEnv", state, self._made_for(),
-                    names + ["_fin_read", "_calls", "generator", "record", "stepper"])
+                    names + ["_fin_read", "_calls", "generator", "record", "stepper"]
+                    + (["_perf_read"] if keep_perf else []))
         self.st.check_state_dict(state["stepper"])
         if self.rec is not None:
             self.rec.check_state_dict(state["record"])
@@ -515,11 +609,14 @@ class BatchedEnv:
             self.rec.load_state_dict(state["record"])
         for name in self._state_tensors():
             have = getattr(self, name)
-            if name in ("obs", "last_action", "t", "steps", "episode_return"):   # replaced, not written, by step()
+            if name in ("obs", "last_action", "t", "steps", "episode_return", "_perf_sum", "_perf_n"):
+                # replaced, not written, by step()
                 setattr(self, name, state[name].to(self.dev))
             else:
                 have.copy_(state[name])
         self._fin_read = int(state["_fin_read"])
+        if self.performance_from is not None:
+            self._perf_read = int(state["_perf_read"])
         self._calls = int(state["_calls"])
         self.gen.set_state(state["generator"])
         if self.rec is not None:

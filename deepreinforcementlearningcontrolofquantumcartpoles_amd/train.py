@@ -22,6 +22,10 @@ the tick that took it, which keeps the loop free of synchronisation and makes th
 
 `python -m deepreinforcementlearningcontrolofquantumcartpoles_amd.train --system iho` builds the objects with the
 drivers' argument names and runs it (one GPU).
+
+`Monitor` (csrc/qcart_monitor.hip) is the cooling drivers' receive_net on the device: the table of their best models,
+ranked by the mean of the last performances of a BatchedEnv made with `performance_from`. A Trainer given one saves
+the outgoing model of a push under its rank, one step late, and evaluates by the performance.
 """
 from __future__ import annotations
 
@@ -122,8 +126,8 @@ class Schedule(L.DeviceHandle):
         drivers t_full = t_max - 0.01 dt (BatchedEnv's t_trunc) and HO's zero-sample rule at one control interval.
         HO has no lr cap and no temporary target period (warm_backup_period = backup_period), and steps its lr while
         last_achieved_time == t_max (HO/main_parallel.py:531) where this schedule, like the other three drivers, asks for
-        learning in progress. The cooling drivers save their best models by performance; here every driver saves by
-        `save_interval`.
+        learning in progress. The cooling drivers save their best models by performance: a Trainer given a
+        `Monitor` ignores this schedule's save flag; without one every driver saves by `save_interval`.
         min_rows defaults to batch_size (TrainDQN returns None below it, RL.py:161)."""
         fam = physics.family
         episodes, sched, lr0, cap, give_up = _DRIVER[fam]
@@ -231,6 +235,152 @@ class Schedule(L.DeviceHandle):
         self.ticks = int.from_bytes(bytes(state["blob"][-8:].tolist()), "little", signed=True)   # the payload's tail
 
 
+_MONITOR_NAMES = ("train", "window", "min_count", "min_episodes", "num_of_saves", "initial")
+# receive_net's rule per cooling driver: (performances averaged, needed since the last net) (QO/main_parallel.py:311-312,
+# HO/main_parallel.py:373-374)
+_MONITOR_RULE = {cfg.QO: (8, 8), cfg.HO: (10, 9)}
+
+
+def performance_from(physics: cfg.Physics, input: str = "xp") -> float:
+    """The episode time past which the cooling drivers count a control step into the episode's performance: the
+    reference's literals, t > 30 (HO 'xp' and 'wavefunction', HO/main_parallel.py:247), t > 30 - 0.01 dt (HO
+    'measurements', :274) and t > 50 - 0.01 dt (QO/main_parallel.py:221). BatchedEnv's performance_from."""
+    if physics.family == cfg.HO:
+        return 30. - 0.01 * physics.dt if input == "measurements" else 30.
+    if physics.family == cfg.QO:
+        return 50. - 0.01 * physics.dt
+    raise ValueError("the cartpole drivers (IHO, IQO) have no per-episode performance")
+
+
+class Monitor(L.DeviceHandle):
+    """The cooling drivers' model ranking on the device (qc_monitor, include/qcart.h): worker_manager.receive_net's
+    table of the num_of_saves best means of the last `window` episode performances, fed from the performance ring of
+    a BatchedEnv made with performance_from. Keyword arguments are qc_monitor_params' fields; `for_driver` fills a
+    driver's. A refused value raises QCartError with the library's text."""
+
+    _prefix = "qc_monitor"
+    DEFAULTS = dict(train=1, window=8, min_count=8, min_episodes=50, num_of_saves=20, initial=6.)
+
+    def __init__(self, device: int | str | torch.device = 0, **params):
+        unknown = set(params) - set(_MONITOR_NAMES)
+        if unknown:
+            raise ValueError(f"Monitor: unknown parameter(s) {sorted(unknown)}")
+        if not torch.cuda.is_available():
+            raise RuntimeError("libqcart needs a HIP device (no CPU fallback)")
+        self.device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        p = dict(self.DEFAULTS, **params)
+        self.params = {k: type(self.DEFAULTS[k])(p[k]) for k in _MONITOR_NAMES}
+        c = L.QcMonitorParams(**self.params)
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            torch.cuda.init()
+            L.check_monitor(L.lib().qc_monitor_create(ctypes.byref(c), self.device.index, ctypes.byref(h)))
+        self._h = h
+        self.calls = 0        # receives enqueued: receive() returns the index of the one it ran
+
+    @classmethod
+    def for_driver(cls, physics: cfg.Physics, num_of_saves: int = 20, energy_cutoff: float = 12.,
+                   phonon_cutoff: float = 20., train: bool = True, device: int | str | torch.device = 0,
+                   **overrides) -> "Monitor":
+        """The ranking of the cooling driver of `physics.family`: QO the last 8 performances with at least 8 new
+        ones, the table starting at energy_cutoff / 2 (QO/main_parallel.py:283, 311-312); HO the last 10 with at
+        least 9 new ones, starting at phonon_cutoff (HO/main_parallel.py:348, 373-374); more than 50 episodes since
+        the last record. The cartpole drivers save by save_interval and have none."""
+        if physics.family not in _MONITOR_RULE:
+            raise ValueError("Monitor.for_driver: the cooling drivers (HO, QO) rank their models by performance; the "
+                             "cartpole drivers (IHO, IQO) save by save_interval")
+        window, min_count = _MONITOR_RULE[physics.family]
+        kw = dict(train=int(bool(train)), window=window, min_count=min_count, min_episodes=50,
+                  num_of_saves=int(num_of_saves),
+                  initial=float(energy_cutoff) / 2. if physics.family == cfg.QO else float(phonon_cutoff))
+        kw.update(overrides)
+        return cls(device=device, **kw)
+
+    # ------------------------------------------------------------------ receives
+    def receive_raw(self, perf: torch.Tensor, fin_cap: int, fin_n: torch.Tensor) -> int:
+        """qc_monitor_receive on a performance ring [fin_cap + 1] float64 and its int64 count; asynchronous. Returns
+        the receive's index."""
+        if perf.dtype != torch.float64 or tuple(perf.shape) != (fin_cap + 1,) or not perf.is_contiguous():
+            raise ValueError("perf must be a contiguous float64 [fin_cap + 1] tensor")
+        if fin_n.dtype != torch.int64 or fin_n.numel() != 1:
+            raise ValueError("fin_n must be one int64")
+        if perf.device != self.device or fin_n.device != self.device:
+            raise ValueError(f"the ring must live on {self.device}")
+        vp = ctypes.c_void_p
+        with torch.cuda.device(self.device):
+            self._bind_stream()
+            self._check(L.lib().qc_monitor_receive(self._h, vp(perf.data_ptr()), int(fin_cap), vp(fin_n.data_ptr())))
+        self.calls += 1
+        return self.calls - 1
+
+    def receive(self, env) -> int:
+        """One receive on `env`'s performance ring (BatchedEnv.performance_ring). Asynchronous: one launch, one
+        snapshot copy, one event. Returns the receive's index."""
+        perf, cap, n = env.performance_ring()
+        return self.receive_raw(perf, cap, n)
+
+    def seek(self, env):
+        """Start at the ring's present end: episodes `env` finished before are not this monitor's (qc_monitor_seek;
+        asynchronous)."""
+        _, _, n = env.performance_ring()
+        with torch.cuda.device(self.device):
+            self._bind_stream()
+            self._check(L.lib().qc_monitor_seek(self._h, ctypes.c_void_p(n.data_ptr())))
+
+    def poll(self, call: int) -> dict:
+        """The snapshot of receive `call` (one of the last two) as a dict of qc_monitor_snapshot's fields; waits for
+        that receive's event only."""
+        s = L.QcMonitorSnapshot()
+        self._check(L.lib().qc_monitor_poll(self._h, int(call), ctypes.byref(s)))
+        return {k: getattr(s, k) for k, _ in L.QcMonitorSnapshot._fields_}
+
+    def stats(self) -> dict:
+        """The last receive's snapshot (waits for it). Raises QCartError if a train = 0 monitor's ring was overrun:
+        more than fin_cap episodes finished between two receives, and the oldest were not counted."""
+        if self.calls == 0:
+            raise ValueError("Monitor.stats: no receive yet")
+        s = self.poll(self.calls - 1)
+        if s["error"] & L.QC_MONITOR_ERR_OVERRUN:
+            raise L.QCartError(-1, "Monitor: the performance ring was overrun between two receives (more than "
+                                   "fin_cap new episodes); the walk went on from the oldest entry still present")
+        return s
+
+    def table(self):
+        """(good, filled): the table's num_of_saves values in increasing order and which of them hold a model, as
+        lists. Synchronises the monitor's stream."""
+        n = self.params["num_of_saves"]
+        good, filled = (ctypes.c_double * n)(), (ctypes.c_int32 * n)()
+        with torch.cuda.device(self.device):
+            self._bind_stream()
+            self._check(L.lib().qc_monitor_table(self._h, good, filled))
+        return list(good), list(filled)
+
+    # ------------------------------------------------------------------ checkpoint
+    def _made_for(self) -> dict:
+        return dict(self.params)
+
+    def state_dict(self) -> dict:
+        """The monitor's whole state as CPU values: the handle's blob (qc_monitor_state_export) with the echo of the
+        params it was made for. Synchronises the monitor's stream."""
+        with torch.cuda.device(self.device):
+            blob = self._export_state()
+        return {"kind": self._prefix, **self._made_for(), "blob": blob}
+
+    def check_state_dict(self, state: dict):
+        """Raise ValueError naming the first param of `state` this monitor was not made with; changes nothing."""
+        L.check_echo(type(self).__name__, state, {"kind": self._prefix, **self._made_for()}, ("blob",))
+
+    def load_state_dict(self, state: dict):
+        """Continue from a `state_dict()`: the next receive gives bit for bit what the saved monitor's would have.
+        The receives before stay with the monitor that ran them: `poll` serves only receives run after the load."""
+        self.check_state_dict(state)
+        with torch.cuda.device(self.device):
+            self._import_state(state["blob"])
+        self.calls = int.from_bytes(bytes(state["blob"][-8:].tolist()), "little", signed=True)   # the payload's tail
+
+
 class Trainer:
     """The drivers' training loop on the device objects: `step()` is one control step,
 
@@ -245,14 +395,31 @@ class Trainer:
 
     The constructor applies the schedule's initial lr and its warm backup period to the learner (Main_System.__init__,
     IHO/main_parallel.py:480-481). Saves go to `save_dir` as 1.pth (newest) .. num_of_saves.pth like receive_net
-    (:391-397), each written to a temporary name and renamed."""
+    (:391-397), each written to a temporary name and renamed.
+
+    With `monitor` (the cooling drivers, QO/main_parallel.py:283-329) the saves are the monitor's table instead: a
+    push calls `monitor.receive(env)` and keeps the outgoing model, the one the actor was acting on; the next step()
+    polls that receive and, if it set a record of rank r, moves r+1.pth .. up by one and writes the kept model as
+    {r+1}.pth, so 1.pth is the best model. The schedule's save flag is ignored, and evaluate() reports the episodes'
+    performance."""
 
     def __init__(self, env, actor, memory, learner, schedule: Schedule, save_dir: Optional[str] = None,
-                 eps: Callable[[float], float] = DQNActor.eps_threshold, num_of_saves: int = 20):
+                 eps: Callable[[float], float] = DQNActor.eps_threshold, num_of_saves: int = 20,
+                 monitor: Optional[Monitor] = None):
         self.env, self.actor, self.memory, self.learner, self.schedule = env, actor, memory, learner, schedule
         self.save_dir, self.eps, self.num_of_saves = save_dir, eps, int(num_of_saves)
         if self.num_of_saves < 1:
             raise ValueError("num_of_saves must be >= 1")
+        self.monitor = monitor
+        if monitor is not None:
+            if int(monitor.params["num_of_saves"]) != self.num_of_saves:
+                raise ValueError(f"Trainer: num_of_saves is {self.num_of_saves}, the monitor's "
+                                 f"{monitor.params['num_of_saves']}: the files are the monitor's table")
+            self._model = self._clone_model()     # the model the actor is acting on (receive_net's `net`)
+            self._stash: Optional[dict] = None    # the outgoing model of the last push, until its receive is polled
+            self._recv = -1                       # that receive's index (-1: none is pending)
+            self._recv_carried: Optional[dict] = None   # a checkpoint's snapshot of its pending receive
+            self.n_filled = 0                     # table entries that hold a model = files 1.pth .. n_filled.pth
         self.meas = env.input == "measurements"
         self.steps_done = 0
         self.tick_index = -1          # the last tick run
@@ -267,9 +434,12 @@ class Trainer:
         learner.set_backup_period(self.backup_period)
 
     def objects(self) -> dict:
-        """The five stateful objects under the names checkpoint.save / load take them by."""
-        return {"env": self.env, "actor": self.actor, "memory": self.memory, "learner": self.learner,
-                "schedule": self.schedule}
+        """The five stateful objects under the names checkpoint.save / load take them by (six with a monitor)."""
+        out = {"env": self.env, "actor": self.actor, "memory": self.memory, "learner": self.learner,
+               "schedule": self.schedule}
+        if self.monitor is not None:
+            out["monitor"] = self.monitor
+        return out
 
     # ------------------------------------------------------------------ one control step
     def _store(self, a, obs, reward, done, info):
@@ -295,7 +465,48 @@ class Trainer:
         else:
             self.losses = []
             return False
+        if self.monitor is not None:
+            self._act_on_receive()
         return self._obey(snap)
+
+    # ------------------------------------------------------------------ ranked saves (a monitor is attached)
+    def _clone_model(self) -> dict:
+        return dict(self.learner.state_dict())    # (device copies already: the learner's own tensors stay its own)
+
+    def _act_on_receive(self):
+        """The receive of the last push, one step late: a record writes the outgoing model of that push as
+        {rank + 1}.pth, the files from there on moving up by one (receive_net, QO/main_parallel.py:313-322)."""
+        if self._recv_carried is not None:
+            s, self._recv_carried = self._recv_carried, None
+        elif self._recv >= 0:
+            s = self.monitor.poll(self._recv)
+        else:
+            return
+        self._recv = -1
+        if s["rank"] >= 0:
+            if self.save_dir is not None:
+                self._save_ranked(int(s["rank"]))
+            self.n_filled = int(s["n_filled"])
+            self.saves = [f"{i}.pth" for i in range(1, self.n_filled + 1)]
+        self._stash = None
+
+    def _save_ranked(self, rank: int):
+        os.makedirs(self.save_dir, exist_ok=True)
+        model = {k: v.cpu() for k, v in self._stash.items()}
+        fd, tmp = tempfile.mkstemp(prefix="model.", suffix=".tmp", dir=self.save_dir)
+        try:
+            with os.fdopen(fd, "wb") as f:
+                torch.save(model, f)
+            # files rank + 1 .. n_filled move up by one; the one beyond num_of_saves falls out
+            for i in range(min(self.n_filled, self.num_of_saves - 1), rank, -1):
+                os.replace(os.path.join(self.save_dir, f"{i}.pth"), os.path.join(self.save_dir, f"{i + 1}.pth"))
+            os.replace(tmp, os.path.join(self.save_dir, f"{rank + 1}.pth"))
+        except BaseException:
+            try:
+                os.unlink(tmp)
+            except OSError:
+                pass
+            raise
 
     def _obey(self, s: dict) -> bool:
         if s["lr"] != self.lr:
@@ -306,8 +517,14 @@ class Trainer:
             self.learner.set_backup_period(self.backup_period)
         self.losses = [self.learner.step(self.memory) for _ in range(s["n_updates"])]
         if s["push"]:
+            if self.monitor is not None:
+                # the outgoing net produced the performances seen so far: it is what a record saves
+                self._recv = self.monitor.receive(self.env)
+                self._stash = self._model
             self.learner.push(self.actor)
-        if s["save"] and self.save_dir is not None:
+            if self.monitor is not None:
+                self._model = self._clone_model()
+        if s["save"] and self.save_dir is not None and self.monitor is None:   # (a monitor saves by performance)
             self._save_model()
         self.acted = s
         return bool(s["stop"])
@@ -354,9 +571,18 @@ class Trainer:
         pending = self._carried
         if pending is None and self.tick_index >= 0:
             pending = self.schedule.poll(self.tick_index)
-        return {"kind": "Trainer", "steps_done": int(self.steps_done), "tick_index": int(self.tick_index),
-                "acted": self.acted, "pending": pending, "lr": float(self.lr),
-                "backup_period": int(self.backup_period), "saves": list(self.saves)}
+        out = {"kind": "Trainer", "steps_done": int(self.steps_done), "tick_index": int(self.tick_index),
+               "acted": self.acted, "pending": pending, "lr": float(self.lr),
+               "backup_period": int(self.backup_period), "saves": list(self.saves)}
+        if self.monitor is not None:
+            # the receive still to be acted on (waits for it) and the two models a resumed run needs for it
+            recv = self._recv_carried
+            if recv is None and self._recv >= 0:
+                recv = self.monitor.poll(self._recv)
+            cpu = lambda m: None if m is None else {k: v.cpu() for k, v in m.items()}   # noqa: E731
+            out.update(monitor_pending=recv, monitor_stash=cpu(self._stash), monitor_model=cpu(self._model),
+                       n_filled=int(self.n_filled))
+        return out
 
     def load_state_dict(self, state: dict):
         """After checkpoint.load of `objects()`: continue the saved run bit for bit. Re-applies the period in force to
@@ -371,6 +597,12 @@ class Trainer:
         self.lr, self.backup_period = float(state["lr"]), int(state["backup_period"])
         self.saves = list(state["saves"])
         self.learner.set_backup_period(self.backup_period)
+        if self.monitor is not None:
+            L.check_echo("Trainer", state, {}, ("monitor_pending", "monitor_stash", "monitor_model", "n_filled"))
+            dev = lambda m: None if m is None else {k: v.to(self.monitor.device) for k, v in m.items()}   # noqa: E731
+            self._recv, self._recv_carried = -1, state["monitor_pending"]
+            self._stash, self._model = dev(state["monitor_stash"]), dev(state["monitor_model"])
+            self.n_filled = int(state["n_filled"])
 
     def save_checkpoint(self, path):
         checkpoint.save(path, self.objects(), extra=self.state_dict())
@@ -385,9 +617,12 @@ class Trainer:
         actor's current weights) act greedily without parameter noise (eps = 0, noisy = False: net.eval(),
         layers.py:40) under a schedule made as this one with train = 0, until at least `episodes` episodes have
         finished. Returns (mean, sem, n) of the episode times of all n episodes finished by then and, given `path`,
-        writes the reference's '{} +- {}' line. Nothing is stored or learned; the env goes on from where it is."""
+        writes the reference's '{} +- {}' line. Nothing is stored or learned; the env goes on from where it is. With a
+        monitor attached the statistic is the cooling drivers': (mean, sem, n) of the episodes' performance."""
         if params is not None:
             self.actor.load(params)
+        if self.monitor is not None:
+            return self._evaluate_performance(episodes, path, max_steps)
         sched = Schedule(device=self.schedule.device, **dict(self.schedule.params, train=0))
         env = self.env
         try:
@@ -403,6 +638,30 @@ class Trainer:
             s = sched.stats()
         finally:
             sched.close()
+        if path is not None:
+            with open(path, "w") as f:
+                f.write("{} +- {}\n".format(s["mean"], s["sem"]))
+        return s["mean"], s["sem"], s["n"]
+
+    def _evaluate_performance(self, episodes: int, path: Optional[str], max_steps: Optional[int]):
+        """evaluate() with a monitor attached: the cooling drivers' --test statistic (QO/main_parallel.py:288-296,
+        364-367), mean and sem of the episodes' performance, from a monitor made as the Trainer's with train = 0 that
+        starts at the ring's end and receives once per control step; the stop condition counts its n."""
+        mon = Monitor(device=self.monitor.device, **dict(self.monitor.params, train=0))
+        env = self.env
+        try:
+            mon.seek(env)
+            call, n_steps = -1, 0
+            while max_steps is None or n_steps < max_steps:
+                a = self.actor.act(env.obs, eps=0.0, noisy=False)
+                env.step(a)
+                n_steps += 1
+                prev, call = call, mon.receive(env)
+                if prev >= 0 and mon.poll(prev)["n"] >= episodes:
+                    break
+            s = mon.stats()
+        finally:
+            mon.close()
         if path is not None:
             with open(path, "w") as f:
                 f.write("{} +- {}\n".format(s["mean"], s["sem"]))
@@ -426,6 +685,8 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--max_updates_per_tick", type=int, default=8)
+    ap.add_argument("--num_of_saves", type=int, default=20)
+    ap.add_argument("--test_energy_cutoff", type=float, default=100., help="qo --test: the episodes' energy cutoff")
     ap.add_argument("--checkpoint", metavar="PATH", default=None, help="written when the run ends")
     ap.add_argument("--resume", metavar="PATH", default=None)
     ap.add_argument("--max_steps", type=int, default=None)
@@ -442,7 +703,15 @@ def main(argv=None):
     fam = {"ho": cfg.HO, "iho": cfg.IHO, "qo": cfg.QO, "iqo": cfg.IQO}[args.system]
     ph = cfg.DEFAULTS[fam]
     B, seed = args.envs, args.seed
-    env = BatchedEnv(ph, B, 0, seed=seed, input=args.input, reset="warmup" if fam == cfg.QO else "deferred")
+    env_kw, monitor = {}, None
+    if fam in (cfg.HO, cfg.QO):
+        # the cooling drivers are measured and saved by the episodes' performance (receive_net)
+        env_kw["performance_from"] = performance_from(ph, args.input)
+        train_cutoff = 12.      # QO/arguments.py: --energy_cutoff
+        if fam == cfg.QO:
+            env_kw["energy_cutoff"] = args.test_energy_cutoff if args.test else train_cutoff   # QO/main_parallel.py:206
+        monitor = Monitor.for_driver(ph, num_of_saves=args.num_of_saves, energy_cutoff=train_cutoff)
+    env = BatchedEnv(ph, B, 0, seed=seed, input=args.input, reset="warmup" if fam == cfg.QO else "deferred", **env_kw)
     # the drivers' learner table: fc2's width, the TD target, LaProp's betas
     hidden2 = 512 if fam in (cfg.QO, cfg.IQO) else 256
     target = {cfg.IHO: "alive", cfg.IQO: "alive", cfg.QO: "reward_fail", cfg.HO: "reward"}[fam]
@@ -469,7 +738,8 @@ def main(argv=None):
         # the drivers' 7000 x n_con x 100 rows (IHO/main_parallel.py:595) for 'xp'; 65 536 wavefunction rows
         row_len, capacity = 2 * Lobs + 2, (7000 * 18 * 100 if args.input == "xp" else 65536)
     memory = PrioritizedReplay(capacity, row_len, "random", 0.2, device=0, seed=seed + 3)
-    trainer = Trainer(env, actor, memory, learner, schedule, save_dir=args.save_dir)
+    trainer = Trainer(env, actor, memory, learner, schedule, save_dir=args.save_dir, num_of_saves=args.num_of_saves,
+                      monitor=monitor)
     if args.resume:
         trainer.load_checkpoint(args.resume)
     else:

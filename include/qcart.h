@@ -652,7 +652,19 @@ int qc_mlearner_state_import(qc_mlearner* l, const void* host_src, uint64_t n);
  *     live. rec_mode, when given, is written as for the other kinds.
  * qc_env_warmup_draw starts the warm-up of the envs with mask[e] != 0 (mask NULL: all) by the same draw and zeroes
  * their t, steps and return; it reads B, kind (QC_QO), interval, dt, pending, t, steps, episode_return and the
- * fields after rec_mode except init_energy_cutoff and reset_out. */
+ * fields after rec_mode except init_energy_cutoff and reset_out.
+ * perf != NULL (QC_HO and QC_QO; a cartpole kind, or perf_sum or perf_n NULL, is QC_EINVAL) adds the episode's
+ * performance, the mean of quantity over the late part of the episode (the drivers' avg_phonon / avg_energy,
+ * HO/main_parallel.py:247-248, 274-275, 294-295; QO/main_parallel.py:221, 231-232). A struct that leaves the four
+ * fields zero behaves as before they existed.
+ *   - episode start (QC_HO: pending on entry; QC_QO: the env goes live; qc_env_warmup_draw): perf_sum = 0, perf_n = 0.
+ *   - a live control step that does not end the episode (QC_HO's pending first control step included) and whose new
+ *     episode time t satisfies t > perf_from: perf_sum += quantity (rounded once), perf_n += 1. A step that ends the
+ *     episode adds nothing: the reference breaks before it accumulates, and at t_max its loop ends first.
+ *   - a finished episode: p = perf_sum / perf_n (rounded once) when t >= t_trunc and perf_n > 0, else cutoff (the
+ *     reference's avg = accu / counter if t == t_max else cutoff; with perf_n == 0 it would divide by zero). p goes
+ *     to perf[i % fin_cap], i the episode's position in fin; perf[fin_cap] is a sink the kernel never writes.
+ *   - a warming QC_QO env touches neither accumulator. */
 typedef struct qc_env_tail_args {
     int64_t B;
     int32_t kind;             /* enum qc_family: QC_IHO or QC_IQO (cartpoles), QC_HO or QC_QO (cooling) */
@@ -688,6 +700,10 @@ typedef struct qc_env_tail_args {
     uint64_t seed;            /* QC_QO: Philox key of the draws */
     int64_t env_offset;       /* QC_QO: global id of env 0 (Philox counter word 2 = env_offset + e) */
     uint8_t* reset_out;       /* [B] QC_QO: 1 where the env went live in this call */
+    double* perf_sum;         /* [B] QC_HO, QC_QO with perf: sum of quantity over the episode's counted control steps */
+    int64_t* perf_n;          /* [B] QC_HO, QC_QO with perf: how many were counted */
+    double* perf;             /* [fin_cap + 1] or NULL: the finished episodes' performance, entry i at i % fin_cap */
+    double perf_from;         /* a control step is counted when its new episode time is > perf_from */
 } qc_env_tail_args;
 int qc_env_tail(qc_handle* h, const qc_env_tail_args* a);
 int qc_env_warmup_draw(qc_handle* h, const qc_env_tail_args* a, const uint8_t* mask);
@@ -774,6 +790,62 @@ int qc_sched_poll(qc_sched* s, int64_t tick, qc_sched_snapshot* out);
 int qc_sched_state_bytes(qc_sched* s, uint64_t* n);
 int qc_sched_state_export(qc_sched* s, void* host_dst, uint64_t n);
 int qc_sched_state_import(qc_sched* s, const void* host_src, uint64_t n);
+
+/* ---- model ranking: the cooling drivers' receive_net on the device --------------------------------------------
+ * worker_manager.receive_net (QO/main_parallel.py:283-329, HO/main_parallel.py:348-388) on the ring of the finished
+ * episodes' performances (qc_env_tail_args.perf): the cooling drivers keep their num_of_saves best models, ranked by
+ * the mean of the last `window` performances seen when a new net arrives. qc_monitor_receive is one launch of one
+ * wave, one asynchronous copy of the snapshot into the call's pinned slot and one event record, as qc_sched_tick.
+ * train == 1 (a net has arrived): fresh = *fin_n - read (negative: 0); count = fresh; episode_passed += fresh; read =
+ * *fin_n. If episode_passed > min_episodes and count >= min_count: new_avg = the mean of the last k = min(count,
+ * window) ring entries, oldest first, summed in numpy's order for these lengths (below 8 a running sum; from 8 on
+ * ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7)), with 16 values a[j] + a[8 + j] in place of a[j], then the
+ * values past the last whole block of 8 one by one; each operation rounded once), divided by k. If new_avg <
+ * good[num_of_saves - 1] the new entry takes rank = the number of the other num_of_saves - 1 entries <= new_avg (the
+ * stable sort of good_actors.sort: ties go behind), the entries from rank on move down by one with their filled
+ * flags, filled[rank] = 1 and episode_passed = 0. count = 0 after every receive (performances.clear()). Only the
+ * last min(fresh, window) entries are read: window <= fin_cap is required, so they are always present and the work
+ * per call is constant; an overrun ring is no error here.
+ * train == 0 (--test): every fresh entry goes into n / sum / sum of squares in ring order; mean and sem as
+ * qc_sched's. More than fin_cap fresh entries raise error bit 0 and the walk starts at the oldest entry present. */
+#define QC_MONITOR_MAX_SAVES 64
+#define QC_MONITOR_MAX_WINDOW 16
+typedef struct qc_monitor_params {
+    int32_t train;                 /* 1: the ranking; 0: the --test sums                                  */
+    int32_t window;                /* performances averaged (QO 8, HO 10); 1 .. 16                        */
+    int32_t min_count;             /* performances needed since the last receive (QO 8, HO 9); 1 .. window */
+    int32_t num_of_saves;          /* 1 .. 64                                                             */
+    int64_t min_episodes;          /* episodes since the last record must be > min_episodes (50)          */
+    double initial;                /* the table's initial values (QO energy_cutoff / 2, HO phonon_cutoff)   */
+} qc_monitor_params;
+typedef struct qc_monitor_snapshot {
+    int64_t call;                  /* 0 for the first qc_monitor_receive                                  */
+    int64_t rank;                  /* the new record's position in the table, -1: none                    */
+    double new_avg;                /* the window mean when the rule was evaluated, else 0                 */
+    int64_t count;                 /* the fresh entries of this receive                                   */
+    int64_t episode_passed;        /* after this receive                                                  */
+    int64_t n_filled;              /* table entries that hold a model                                     */
+    int64_t total_episodes;
+    int64_t error;                 /* sticky; bit 0: the ring was overrun (train == 0)                    */
+    double mean, sem;              /* train == 0: of the performances so far (sem 0 below two)            */
+    int64_t n;
+} qc_monitor_snapshot;
+typedef struct qc_monitor qc_monitor;
+int qc_monitor_create(const qc_monitor_params* p, int device, qc_monitor** out);
+void qc_monitor_destroy(qc_monitor* m);
+const char* qc_monitor_last_error(const qc_monitor* m);
+int qc_monitor_set_stream(qc_monitor* m, void* stream);
+/* asynchronous. perf [fin_cap + 1] and fin_n are device pointers as qc_env_tail_args has them */
+int qc_monitor_receive(qc_monitor* m, const double* perf, int64_t fin_cap, const int64_t* fin_n);
+/* asynchronous, one small launch: read = *fin_n, the ring's present end */
+int qc_monitor_seek(qc_monitor* m, const int64_t* fin_n);
+/* waits on the event of that receive only; the last two are kept, any other is QC_EINVAL */
+int qc_monitor_poll(qc_monitor* m, int64_t call, qc_monitor_snapshot* out);
+/* good [num_of_saves] and filled [num_of_saves] (host pointers, either may be NULL); synchronises the stream */
+int qc_monitor_table(qc_monitor* m, double* good, int32_t* filled);
+int qc_monitor_state_bytes(qc_monitor* m, uint64_t* n);
+int qc_monitor_state_export(qc_monitor* m, void* host_dst, uint64_t n);
+int qc_monitor_state_import(qc_monitor* m, const void* host_src, uint64_t n);
 
 /* ---- step server: the reference's process model on one GPU ------------------------------------------------
  * The drivers run 30-40 actor processes, each with its own `simulation` module stepping ONE env per call
