@@ -8,11 +8,12 @@ Modules:
   env         BatchedEnv: reset/step/observation semantics of the reference drivers, batched
   distributed env sharding over ranks + RCCL gather of episode returns
   learner     DQNLearner / MeasurementLearner: the reference's TrainDQN update on the device
+  spatial     SpatialView: the drivers' spatial_repr / probability (position-space density) of a batch of states
   checkpoint  save / load of the whole device loop; the resumed run is the uninterrupted one bit for bit
 """
 from .config import DEFAULTS, HO, IHO, IQO, QO, Physics  # noqa: F401
 
-__all__ = ["DEFAULTS", "HO", "IHO", "QO", "IQO", "Physics", "DQNLearner", "MeasurementLearner"]
+__all__ = ["DEFAULTS", "HO", "IHO", "QO", "IQO", "Physics", "DQNLearner", "MeasurementLearner", "SpatialView"]
 
 
 def __getattr__(name):
@@ -20,4 +21,7 @@ def __getattr__(name):
     if name in ("DQNLearner", "MeasurementLearner"):
         from . import learner
         return getattr(learner, name)
+    if name == "SpatialView":
+        from . import spatial
+        return spatial.SpatialView
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -53,6 +53,8 @@ EXPORTS = (
     "qc_sched_poll", "qc_sched_seek",
     "qc_monitor_create", "qc_monitor_destroy", "qc_monitor_last_error", "qc_monitor_set_stream", "qc_monitor_receive",
     "qc_monitor_poll", "qc_monitor_seek", "qc_monitor_table",
+    "qc_spatial_create", "qc_spatial_destroy", "qc_spatial_last_error", "qc_spatial_set_stream", "qc_spatial_table",
+    "qc_spatial_repr", "qc_spatial_probability", "qc_spatial_mean",
 ) + tuple(f"qc_{kind}_state_{op}" for kind in ("actor", "mactor", "replay", "learner", "mlearner", "sched", "monitor")
           for op in ("bytes", "export", "import"))   # checkpoint: a handle's whole state as one host buffer
 
@@ -499,6 +501,16 @@ def lib() -> ctypes.CDLL:
     L.qc_monitor_poll.argtypes = [vp, i64, P(QcMonitorSnapshot)]
     L.qc_monitor_seek.argtypes = [vp, vp]
     L.qc_monitor_table.argtypes = [vp, vp, vp]
+    L.qc_spatial_create.argtypes = [i32, vp, i32, ctypes.c_int, P(vp)]
+    L.qc_spatial_destroy.argtypes = [vp]
+    L.qc_spatial_destroy.restype = None
+    L.qc_spatial_last_error.argtypes = [vp]
+    L.qc_spatial_last_error.restype = ctypes.c_char_p
+    L.qc_spatial_set_stream.argtypes = [vp, vp]
+    L.qc_spatial_table.argtypes = [vp, vp]
+    L.qc_spatial_repr.argtypes = [vp, vp, i32, i32, d, vp]
+    L.qc_spatial_probability.argtypes = [vp, vp, i32, i32, d, vp]
+    L.qc_spatial_mean.argtypes = [vp, vp, i32, i32, vp, d, vp, vp]
     L.qc_mlearner_stats.argtypes = [vp, P(QcLearnerStats)]
     L.qc_mlearner_grads.argtypes = [vp, P(QcDqnLayer)]
     L.qc_mlearner_apply.argtypes = [vp, P(QcDqnLayer)]
@@ -553,6 +565,7 @@ check_mlearner = _checker("qc_mlearner")
 check_replay = _checker("qc_replay")
 check_sched = _checker("qc_sched")
 check_monitor = _checker("qc_monitor")
+check_spatial = _checker("qc_spatial")
 
 
 class DeviceHandle:

@@ -632,6 +632,17 @@ class BatchedEnv:
         act, _ = self.st.control(self.psi, strategy, con_parameter, input_scaling=sc)
         return act
 
+    def probability(self, view, mean: bool = False, mask: Optional[torch.Tensor] = None):
+        """The position-space density of the current states through a spatial.SpatialView made for this physics
+        (SpatialView.for_physics): `view.probability(self.psi)` [B, X], or with mean = True
+        `view.mean_probability(self.psi, mask)`, the pair (ensemble mean [X], count) over the envs whose mask is set.
+        Reads psi only: the env's state is unchanged."""
+        if mean:
+            return view.mean_probability(self.psi, mask)
+        if mask is not None:
+            raise ValueError("BatchedEnv.probability: mask goes with mean = True")
+        return view.probability(self.psi)
+
     @staticmethod
     def experience(last_obs: torch.Tensor, obs: torch.Tensor, action: torch.Tensor, reward: torch.Tensor):
         """Experience rows in the reference layout np.hstack((last_data, data, [last_action], [reward]))."""

@@ -612,17 +612,22 @@ class Trainer:
 
     # ------------------------------------------------------------------ --test
     def evaluate(self, params: Optional[Mapping[str, torch.Tensor]], episodes: int, path: Optional[str] = None,
-                 max_steps: Optional[int] = None):
+                 max_steps: Optional[int] = None, density=None):
         """The drivers' --test mode (IHO/main_parallel.py:367-377, 442-445): `params` (a state_dict; None: the
         actor's current weights) act greedily without parameter noise (eps = 0, noisy = False: net.eval(),
         layers.py:40) under a schedule made as this one with train = 0, until at least `episodes` episodes have
         finished. Returns (mean, sem, n) of the episode times of all n episodes finished by then and, given `path`,
         writes the reference's '{} +- {}' line. Nothing is stored or learned; the env goes on from where it is. With a
-        monitor attached the statistic is the cooling drivers': (mean, sem, n) of the episodes' performance."""
+        monitor attached the statistic is the cooling drivers': (mean, sem, n) of the episodes' performance.
+        `density` (a spatial.SpatialView for the env's physics): every control step appends the ensemble mean
+        position-space density of the envs that were live at that step (info['valid']) to `self.density_trace`, a
+        list of device [X] tensors that starts empty with each call; nothing in the loop waits for them and the
+        returned tuple is the same."""
         if params is not None:
             self.actor.load(params)
+        self.density_trace: list = []
         if self.monitor is not None:
-            return self._evaluate_performance(episodes, path, max_steps)
+            return self._evaluate_performance(episodes, path, max_steps, density)
         sched = Schedule(device=self.schedule.device, **dict(self.schedule.params, train=0))
         env = self.env
         try:
@@ -630,7 +635,9 @@ class Trainer:
             tick, n_steps = -1, 0
             while max_steps is None or n_steps < max_steps:
                 a = self.actor.act(env.obs, eps=0.0, noisy=False)
-                env.step(a)
+                info = env.step(a)[3]
+                if density is not None:
+                    self.density_trace.append(env.probability(density, mean=True, mask=info["valid"])[0])
                 n_steps += 1
                 prev, tick = tick, sched.tick(env, None)
                 if prev >= 0 and sched.poll(prev)["n"] >= episodes:
@@ -643,7 +650,7 @@ class Trainer:
                 f.write("{} +- {}\n".format(s["mean"], s["sem"]))
         return s["mean"], s["sem"], s["n"]
 
-    def _evaluate_performance(self, episodes: int, path: Optional[str], max_steps: Optional[int]):
+    def _evaluate_performance(self, episodes: int, path: Optional[str], max_steps: Optional[int], density=None):
         """evaluate() with a monitor attached: the cooling drivers' --test statistic (QO/main_parallel.py:288-296,
         364-367), mean and sem of the episodes' performance, from a monitor made as the Trainer's with train = 0 that
         starts at the ring's end and receives once per control step; the stop condition counts its n."""
@@ -654,7 +661,9 @@ class Trainer:
             call, n_steps = -1, 0
             while max_steps is None or n_steps < max_steps:
                 a = self.actor.act(env.obs, eps=0.0, noisy=False)
-                env.step(a)
+                info = env.step(a)[3]
+                if density is not None:
+                    self.density_trace.append(env.probability(density, mean=True, mask=info["valid"])[0])
                 n_steps += 1
                 prev, call = call, mon.receive(env)
                 if prev >= 0 and mon.poll(prev)["n"] >= episodes:
@@ -691,6 +700,8 @@ def main(argv=None):
     ap.add_argument("--resume", metavar="PATH", default=None)
     ap.add_argument("--max_steps", type=int, default=None)
     ap.add_argument("--report_every", type=int, default=100)
+    ap.add_argument("--density_out", metavar="PATH", default=None,
+                    help="--test: x and the ensemble density per control step of the first model evaluated, one .npz")
     args = ap.parse_args(argv)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("train: one GPU only; WORLD_SIZE > 1 is refused (multi-GPU training is not built)")
@@ -748,10 +759,19 @@ def main(argv=None):
         n_test = args.num_of_test_episodes or {cfg.IHO: 4000, cfg.IQO: 4000, cfg.HO: 500, cfg.QO: 300}[fam]
         folder = args.load_dir or args.save_dir
         names = sorted((f for f in os.listdir(folder) if f.endswith(".pth")), key=lambda f: int(f[:-4]))
-        for name in names:
+        view = None
+        if args.density_out:
+            from .spatial import SpatialView
+            view = SpatialView.for_physics(ph)
+        for i, name in enumerate(names):
             model = torch.load(os.path.join(folder, name), map_location="cuda", weights_only=True)
-            mean, sem, n = trainer.evaluate(model, n_test, path=os.path.join(folder, name[:-4] + ".txt"))
+            mean, sem, n = trainer.evaluate(model, n_test, path=os.path.join(folder, name[:-4] + ".txt"),
+                                            density=view if i == 0 else None)
             print(f"{name}: {mean} +- {sem} ({n} episodes)", flush=True)
+            if view is not None and i == 0:
+                import numpy as np
+                np.savez(args.density_out, x=view.x.cpu().numpy(),
+                         density=torch.stack(trainer.density_trace).cpu().numpy())
         return 0
     steps = trainer.run(args.max_steps, report_every=args.report_every)
     s = trainer.schedule.stats()

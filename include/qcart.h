@@ -847,6 +847,40 @@ int qc_monitor_state_bytes(qc_monitor* m, uint64_t* n);
 int qc_monitor_state_export(qc_monitor* m, void* host_dst, uint64_t n);
 int qc_monitor_state_import(qc_monitor* m, const void* host_src, uint64_t n);
 
+/* ---- position-space view: the drivers' spatial_repr and probability on the device ---------------------------------
+ * HO/main_parallel.py:47-51, 82-86, 100-102 (IHO alike): the wavefunction of a Fock-basis state on a grid x,
+ * phi[b][j] = sum_n E[j][n] c[b][n] with the table E[j][n] = psi_n(x[j]) of the normalised harmonic-oscillator
+ * eigenfunctions (hbar = m = omega = 1), and its density p[b][j] = fl(fl(Re phi^2) + fl(Im phi^2)). The table is built
+ * on the host at create time in long double by the upward three-term recurrence and rounded once to fp64
+ * (csrc/qcart_spatial.hpp): n_levels in [1, 2048], x_n in [1, 4096], every x finite with |x| <= 128.
+ * n_levels == 0 makes a grid view (QO / IQO, whose state already lives on x): no table, n_state must equal x_n,
+ * probability is |psi_j|^2 by the same formula, repr is refused (the state is its own representation).
+ * psi is [B][n_state] complex128 on the device, n_state <= n_levels: a shorter state uses the table's first columns.
+ * threshold >= 0: a level takes part only if hypot(Re c, Im c) > threshold (the drivers' display mask is 1e-4); a
+ * masked level contributes an exact zero; a grid view ignores it. phi[b] does not depend on B or on where env b sits.
+ * qc_spatial_mean: m[j] = (sum over the envs b with mask[b] != 0 (mask NULL: all) of p[b][j]) / count, and count
+ * itself; count == 0 gives zeros. The order of the sum is fixed by (B, X) alone: the envs form groups of 32 (group
+ * g = envs 32 g .. 32 g + 31; envs past B and masked envs enter as +0); within a group s[q] (q = 0 .. 3) = the running
+ * sum, from +0, of p of the group's envs q, q + 4, .., q + 28 in that order, and the group's partial is
+ * (s[0] + s[1]) + (s[2] + s[3]); the same rule one level up: r[t] (t = 0 .. 3) = the running sum, from +0, of the
+ * partials of the groups t, t + 4, t + 8, .. in that order, and m[j] = ((r[0] + r[1]) + (r[2] + r[3])) /
+ * (double)count. Every operation is rounded once; no atomics. The partials live in a buffer the handle owns (it grows
+ * with B). All calls are asynchronous on the bound stream. */
+typedef struct qc_spatial qc_spatial;
+int qc_spatial_create(int32_t n_levels, const double* x /* host [x_n] */, int32_t x_n, int device, qc_spatial** out);
+void qc_spatial_destroy(qc_spatial* s);
+const char* qc_spatial_last_error(const qc_spatial* s);
+int qc_spatial_set_stream(qc_spatial* s, void* stream);
+/* out: device [x_n][n_levels], a copy of the table; a grid view has none (QC_EINVAL) */
+int qc_spatial_table(const qc_spatial* s, double* out);
+/* out: device [B][x_n] complex128 */
+int qc_spatial_repr(qc_spatial* s, const void* psi, int32_t B, int32_t n_state, double threshold, void* out);
+/* out: device [B][x_n] */
+int qc_spatial_probability(qc_spatial* s, const void* psi, int32_t B, int32_t n_state, double threshold, double* out);
+/* mask: device uint8 [B] or NULL; out: device [x_n]; count: device, may be NULL */
+int qc_spatial_mean(qc_spatial* s, const void* psi, int32_t B, int32_t n_state, const uint8_t* mask, double threshold,
+                    double* out, int64_t* count);
+
 /* ---- step server: the reference's process model on one GPU ------------------------------------------------
  * The drivers run 30-40 actor processes, each with its own `simulation` module stepping ONE env per call
  * (IHO/main_parallel.py:345-359, :264). A step server owns one handle of batch max_clients (env e = client slot
