@@ -2,7 +2,8 @@
 //
 // -DQCART_STAMPS (a diagnostic build only, tools/diag_stamps.py): per-phase cycle shares of the step loop
 // (s_memtime at each QC_STAMP(phase) site of qcart_kernels.hpp), summed over all waves into qc_stamps[] and
-// read back by qc_debug_stamps. Without it every hook below expands to nothing.
+// read back by qc_debug_stamps. -DQCART_BSTAMPS (tools/diag_boundaries.py): four stamps per wave around the loop, for
+// the cost of a workgroup boundary. Without either every hook below expands to nothing.
 //
 // Experiment knobs: compile-time defaults of the shipped build that an experiment build (make expt / expt_actor
 // EXPT=-D...) overrides for an A/B. Each default is the measured winner.
@@ -40,6 +41,17 @@
 // held in 4 VGPRs across the step loop (0) — fp64 kernels with LDS tables (MODE >= 1)
 #ifndef QCART_NZ_LDS
 #define QCART_NZ_LDS 1
+#endif
+// step kernel, 8-wave fp64 Fock workgroups with LDS tables: the two waves of a SIMD balanced by progress — each
+// publishes its step index in LDS and the one behind issues at s_setprio 1 (kPairBalance, qcart_kernels.hpp; 0: the
+// hardware's older-first arbitration. Metric, four alternating same-call pairs: 23.64 -> 22.74 ms per launch,
+// profiles/r07_pair_balance_ab.txt), for kernels of at least QCART_PAIR_BALANCE_MIN_R rows per lane (8: IHO N = 512,
+// the measured shape, and HO N = 512; smaller R not measured)
+#ifndef QCART_PAIR_BALANCE
+#define QCART_PAIR_BALANCE 1
+#endif
+#ifndef QCART_PAIR_BALANCE_MIN_R
+#define QCART_PAIR_BALANCE_MIN_R 8
 #endif
 // measurement actor (qcart_actor.hip): conv1..3 column tiles per wave, accumulator sets, k-steps per load batch;
 // fc1 output tiles x env tiles per wave
@@ -115,6 +127,59 @@ extern "C" __attribute__((weak)) int qc_debug_stamps(unsigned long long* out) {
     if (hipMemcpyFromSymbol(out, HIP_SYMBOL(qcart::qc_stamps), sizeof(unsigned long long) * 20) != hipSuccess) return -1;
     unsigned long long z[20] = {0};
     return hipMemcpyToSymbol(HIP_SYMBOL(qcart::qc_stamps), z, sizeof(z)) == hipSuccess ? 0 : -1;
+}
+#elif defined(QCART_BSTAMPS)
+// -DQCART_BSTAMPS (a diagnostic build only, tools/diag_boundaries.py): the cost of a workgroup boundary. Every wave
+// that runs a tile reads s_memtime at kernel (tile) entry, loop begin, loop end and exit, and lane 0 writes the four
+// values and the wave's hardware id (HW_ID: CU / SH / SE, and XCC_ID) with plain vector stores into the wave's own
+// record of qc_bstamps — no atomics, nothing shared between waves. Record of tile t's wave w: (t * W + w) * 8 words
+// (tile: the workgroup's place in the launch, the a.n_mixed two-slot tiles first). qc_debug_bstamps copies the
+// records out and clears them.
+namespace qcart {
+constexpr unsigned kBStampWaves = 1u << 17;
+__device__ unsigned long long qc_bstamps[kBStampWaves * 8];
+}
+#define QC_STAMP(ph) \
+    do {             \
+    } while (0)
+#define QC_BSTAMP_READ(t_) asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_)::"memory")
+#define QC_KSTAMP_ENTRY()        \
+    unsigned long long bst_t0;   \
+    QC_BSTAMP_READ(bst_t0)
+#define QC_STAMP_BEGIN()         \
+    unsigned long long bst_t1;   \
+    QC_BSTAMP_READ(bst_t1)
+#define QC_STAMP_END(lane)       \
+    unsigned long long bst_t2;   \
+    QC_BSTAMP_READ(bst_t2)
+// (blk, a, ei, MODE and W are step_body's: the tile index counts the a.n_mixed two-slot tiles first)
+#define QC_KSTAMP_EXIT(lane)                                                                         \
+    do {                                                                                             \
+        unsigned long long t_;                                                                       \
+        QC_BSTAMP_READ(t_);                                                                          \
+        const unsigned w_ = ((MODE == 3 ? 0u : a.n_mixed) + (unsigned)(blk)) * (unsigned)W + (unsigned)ei; \
+        if ((lane) == 0 && w_ < kBStampWaves) {                                                      \
+            const unsigned hw_ = __builtin_amdgcn_s_getreg(4 | (31 << 11));   /* HW_ID[31:0] */      \
+            const unsigned xc_ = __builtin_amdgcn_s_getreg(20 | (3 << 11));   /* XCC_ID[3:0] */      \
+            unsigned long long* p_ = qc_bstamps + (size_t)w_ * 8;                                    \
+            p_[0] = bst_t0;                                                                          \
+            p_[1] = bst_t1;                                                                          \
+            p_[2] = bst_t2;                                                                          \
+            p_[3] = t_;                                                                              \
+            p_[4] = ((unsigned long long)xc_ << 32) | hw_;                                           \
+            p_[5] = blockIdx.x;                                                                      \
+        }                                                                                            \
+    } while (0)
+#define QC_SOLVE_STAMP_ARGS
+#define QC_SOLVE_STAMP_PASS
+// copy the first n_waves records out (8 words each) and clear them (weak: an experiment build stamps one family TU)
+extern "C" __attribute__((weak)) int qc_debug_bstamps(unsigned long long* out, unsigned n_waves) {
+    if (n_waves > qcart::kBStampWaves) return -1;
+    const size_t bytes = sizeof(unsigned long long) * 8 * (size_t)n_waves;
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(qcart::qc_bstamps), bytes) != hipSuccess) return -1;
+    void* p = nullptr;
+    if (hipGetSymbolAddress(&p, HIP_SYMBOL(qcart::qc_bstamps)) != hipSuccess) return -1;
+    return hipMemset(p, 0, bytes) == hipSuccess ? 0 : -1;
 }
 #else
 #define QC_STAMP(ph) \

@@ -1286,6 +1286,21 @@ template <int FAM, int R, typename RT = double>
 constexpr int kStepWaves =
     ((FAM <= 1 && R * (int)sizeof(RT) / 8 <= QCART_W8_MAX_R) || (FAM == 2 && R <= QCART_W8_MAX_RG)) ? 8 : 4;
 
+// pair balance (QCART_PAIR_BALANCE, qcart_expt.hpp): waves w and w + 4 of an 8-wave workgroup share a SIMD, and the
+// hardware issues the older one's VALU first — at the metric shape waves 0-3 finished their 80 steps after 0.95 M
+// cycles and waves 4-7 after 1.53 M, so every SIMD ran one wave for the last 37 % of the workgroup
+// (profiles/r07_metric_boundaries.txt). Each wave publishes its step index in LDS and the one behind issues at
+// s_setprio 1: the pair finishes together (last exit - first exit 580 K -> 19 K cycles per SIMD) and the workgroup
+// takes 9.1 % fewer cycles, 3.8 % less time. Priority and two LDS words per step only: every env's
+// arithmetic is unchanged. The MODE 2 body (single-slot tiles, tables and composites in LDS) of the fp64 Fock kernels
+// with R >= QCART_PAIR_BALANCE_MIN_R rows per lane; the 8 step indices live at a compile-time LDS address above every
+// image, 159 KiB (from a.lds_bytes they cost the two-slot kernels 3 to 6 more spilled SGPRs): launch_step_mode asks
+// for LDS up to there (the workgroup has the CU's 160 KiB to itself: two waves per SIMD)
+template <int FAM, int R, typename RT>
+constexpr bool kPairBalance = QCART_PAIR_BALANCE && FAM <= 1 && sizeof(RT) == 8 && kStepWaves<FAM, R, RT> == 8 &&
+                              R >= QCART_PAIR_BALANCE_MIN_R;
+constexpr uint32_t kPbLds = 64, kPbLdsAt = 159u * 1024u;
+
 
 // lazy normalisation's guard: the carried scale scl = 1/|psi| multiplies up over the steps of a call; a
 // diverging env (past its Fail, where the scheme amplifies the top Fock levels / the grid edges, up to ~1e10
@@ -1601,8 +1616,20 @@ __device__ __forceinline__ void step_body(const KArgs& a, const int32_t* order, 
     // kernel (C5), where the loop-carried scale costs the R = 32 kernel spills
     constexpr bool LAZY = sizeof(RT) == 8;
     double scl = 1.0, sq = 1.0;
+    constexpr bool PB = kPairBalance<FAM, R, RT> && MODE == 2 && !RES;
     QC_STAMP_BEGIN();
     for (int k = 0; k < n_my; ++k) {
+        if constexpr (PB) {
+            // pair balance: the wave publishes its step index (every lane stores the same word) and reads its SIMD
+            // partner's; the one behind issues at priority 1. A stale or idle partner's word only misplaces the
+            // priority: no result depends on it
+            volatile int* const pb = (volatile int*)(simg0 + kPbLdsAt);
+            int eo = ei;   // (opaque per step: the two word addresses are not held in registers across the loop)
+            asm volatile("" : "+v"(eo));
+            pb[eo] = k;
+            __builtin_amdgcn_s_setprio(0);
+            if (__builtin_amdgcn_readfirstlane(pb[eo ^ 4]) > k) __builtin_amdgcn_s_setprio(1);
+        }
         // KAR: the loop's uniform constants are re-read from the kernarg segment every step (s_load through
         // the scalar cache; the opaque pointer keeps the compiler from hoisting them) instead of held in SGPRs
         // across the loop: at 106 SGPRs the metric kernel spilled ~90 of them into VGPR lanes (v_writelane /
@@ -2210,6 +2237,10 @@ __device__ __forceinline__ void step_body(const KArgs& a, const int32_t* order, 
         }   // Fock families
     }
     QC_STAMP_END(lane);
+    if constexpr (PB) {   // done: the partner runs on at priority 1
+        __builtin_amdgcn_s_setprio(0);
+        ((volatile int*)(simg0 + kPbLdsAt))[ei] = 0x7fffffff;
+    }
     if constexpr (LAZY) {
 #pragma unroll
         for (int j = 0; j < R; ++j) psi[j] = C(psi[j].re * (RT)scl, psi[j].im * (RT)scl);   // normalised
@@ -2852,6 +2883,8 @@ template <int FAM, int R, int MODE, typename RT, bool DUAL = false>
 int launch_step_mode(const KArgs& a, hipStream_t st) {
     const dim3 grid(a.n_blocks + (DUAL ? a.n_mixed : 0u)), block(64 * kStepWaves<FAM, R, RT>);
     constexpr bool lds = MODE >= 1;
+    constexpr bool pbal = MODE == 2 && kPairBalance<FAM, R, RT>;   // the pair-balance words: above the images
+    if (pbal && a.lds_bytes > kPbLdsAt) return -3;
     if (lds) {
         static bool attr_set = false;   // allow > 64 KiB of dynamic LDS (gfx950: 160 KiB per CU)
         if (!attr_set) {
@@ -2861,7 +2894,8 @@ int launch_step_mode(const KArgs& a, hipStream_t st) {
             attr_set = true;
         }
     }
-    hipLaunchKernelGGL((k_step<FAM, R, MODE, RT, DUAL>), grid, block, lds ? a.lds_bytes : 0, st, a);
+    hipLaunchKernelGGL((k_step<FAM, R, MODE, RT, DUAL>), grid, block,
+                       pbal ? kPbLdsAt + kPbLds : (lds ? a.lds_bytes : 0u), st, a);
     return 0;
 }
 // per-family launch entry points, instantiated in qcart_k_{ho,iho,grid,f32}.hip
