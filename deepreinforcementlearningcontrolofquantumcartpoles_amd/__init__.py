@@ -9,11 +9,13 @@ Modules:
   distributed env sharding over ranks + RCCL gather of episode returns
   learner     DQNLearner / MeasurementLearner: the reference's TrainDQN update on the device
   spatial     SpatialView: the drivers' spatial_repr / probability (position-space density) of a batch of states
+  wigner      WignerView: the Wigner function (phase-space view) of a batch of states and its ensemble mean
   checkpoint  save / load of the whole device loop; the resumed run is the uninterrupted one bit for bit
 """
 from .config import DEFAULTS, HO, IHO, IQO, QO, Physics  # noqa: F401
 
-__all__ = ["DEFAULTS", "HO", "IHO", "QO", "IQO", "Physics", "DQNLearner", "MeasurementLearner", "SpatialView"]
+__all__ = ["DEFAULTS", "HO", "IHO", "QO", "IQO", "Physics", "DQNLearner", "MeasurementLearner", "SpatialView",
+           "WignerView"]
 
 
 def __getattr__(name):
@@ -24,4 +26,7 @@ def __getattr__(name):
     if name == "SpatialView":
         from . import spatial
         return spatial.SpatialView
+    if name == "WignerView":
+        from . import wigner
+        return wigner.WignerView
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -55,6 +55,8 @@ EXPORTS = (
     "qc_monitor_poll", "qc_monitor_seek", "qc_monitor_table",
     "qc_spatial_create", "qc_spatial_destroy", "qc_spatial_last_error", "qc_spatial_set_stream", "qc_spatial_table",
     "qc_spatial_repr", "qc_spatial_probability", "qc_spatial_mean",
+    "qc_wigner_create", "qc_wigner_destroy", "qc_wigner_last_error", "qc_wigner_set_stream", "qc_wigner_eval",
+    "qc_wigner_mean", "qc_wigner_chunk", "qc_wigner_splits",
 ) + tuple(f"qc_{kind}_state_{op}" for kind in ("actor", "mactor", "replay", "learner", "mlearner", "sched", "monitor")
           for op in ("bytes", "export", "import"))   # checkpoint: a handle's whole state as one host buffer
 
@@ -511,6 +513,16 @@ def lib() -> ctypes.CDLL:
     L.qc_spatial_repr.argtypes = [vp, vp, i32, i32, d, vp]
     L.qc_spatial_probability.argtypes = [vp, vp, i32, i32, d, vp]
     L.qc_spatial_mean.argtypes = [vp, vp, i32, i32, vp, d, vp, vp]
+    L.qc_wigner_create.argtypes = [i32, d, vp, i32, ctypes.c_int, P(vp)]
+    L.qc_wigner_destroy.argtypes = [vp]
+    L.qc_wigner_destroy.restype = None
+    L.qc_wigner_last_error.argtypes = [vp]
+    L.qc_wigner_last_error.restype = ctypes.c_char_p
+    L.qc_wigner_set_stream.argtypes = [vp, vp]
+    L.qc_wigner_eval.argtypes = [vp, vp, i32, vp]
+    L.qc_wigner_mean.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.qc_wigner_chunk.argtypes = [i32]
+    L.qc_wigner_splits.argtypes = [i32, i32, i32]
     L.qc_mlearner_stats.argtypes = [vp, P(QcLearnerStats)]
     L.qc_mlearner_grads.argtypes = [vp, P(QcDqnLayer)]
     L.qc_mlearner_apply.argtypes = [vp, P(QcDqnLayer)]
@@ -566,6 +578,7 @@ check_replay = _checker("qc_replay")
 check_sched = _checker("qc_sched")
 check_monitor = _checker("qc_monitor")
 check_spatial = _checker("qc_spatial")
+check_wigner = _checker("qc_wigner")
 
 
 class DeviceHandle:

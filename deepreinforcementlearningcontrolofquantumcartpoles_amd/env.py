@@ -643,6 +643,17 @@ class BatchedEnv:
             raise ValueError("BatchedEnv.probability: mask goes with mean = True")
         return view.probability(self.psi)
 
+    def wigner(self, view, mean: bool = False, mask: Optional[torch.Tensor] = None):
+        """The Wigner function of the current states through a wigner.WignerView made for this physics
+        (WignerView.for_physics): `view.wigner(self.psi)` [B, X, P], or with mean = True
+        `view.mean_wigner(self.psi, mask)`, the pair (ensemble mean [X, P], count) over the envs whose mask is set.
+        Reads psi only: the env's state is unchanged."""
+        if mean:
+            return view.mean_wigner(self.psi, mask)
+        if mask is not None:
+            raise ValueError("BatchedEnv.wigner: mask goes with mean = True")
+        return view.wigner(self.psi)
+
     @staticmethod
     def experience(last_obs: torch.Tensor, obs: torch.Tensor, action: torch.Tensor, reward: torch.Tensor):
         """Experience rows in the reference layout np.hstack((last_data, data, [last_action], [reward]))."""

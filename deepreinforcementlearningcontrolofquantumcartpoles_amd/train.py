@@ -612,7 +612,8 @@ class Trainer:
 
     # ------------------------------------------------------------------ --test
     def evaluate(self, params: Optional[Mapping[str, torch.Tensor]], episodes: int, path: Optional[str] = None,
-                 max_steps: Optional[int] = None, density=None):
+                 max_steps: Optional[int] = None, density=None, wigner=None,
+                 controller: Optional[tuple] = None):
         """The drivers' --test mode (IHO/main_parallel.py:367-377, 442-445): `params` (a state_dict; None: the
         actor's current weights) act greedily without parameter noise (eps = 0, noisy = False: net.eval(),
         layers.py:40) under a schedule made as this one with train = 0, until at least `episodes` episodes have
@@ -622,22 +623,35 @@ class Trainer:
         `density` (a spatial.SpatialView for the env's physics): every control step appends the ensemble mean
         position-space density of the envs that were live at that step (info['valid']) to `self.density_trace`, a
         list of device [X] tensors that starts empty with each call; nothing in the loop waits for them and the
-        returned tuple is the same."""
-        if params is not None:
-            self.actor.load(params)
+        returned tuple is the same. `wigner` (a wigner.WignerView for the env's physics) does the same with the
+        ensemble mean Wigner function, [X, P] tensors in `self.wigner_trace`.
+        `controller` = (strategy, con_parameter): the drivers' baseline runs (--control_strategy / --con_parameter,
+        QO/main_parallel.py:166-176; --LQG, IHO/main_parallel.py:194-206): the actions come from
+        env.analytic_actions(strategy, con_parameter) and the actor is not touched; `params` must be None."""
+        if controller is not None:
+            if params is not None:
+                raise ValueError("Trainer.evaluate: params and controller exclude each other (a baseline has no net)")
+            strategy, con_parameter = controller
+            act = lambda env: env.analytic_actions(strategy, float(con_parameter))   # noqa: E731
+        else:
+            if params is not None:
+                self.actor.load(params)
+            act = lambda env: self.actor.act(env.obs, eps=0.0, noisy=False)   # noqa: E731
         self.density_trace: list = []
+        self.wigner_trace: list = []
         if self.monitor is not None:
-            return self._evaluate_performance(episodes, path, max_steps, density)
+            return self._evaluate_performance(episodes, path, max_steps, density, wigner, act)
         sched = Schedule(device=self.schedule.device, **dict(self.schedule.params, train=0))
         env = self.env
         try:
             sched.seek(env)          # the ring's earlier episodes are not this evaluation's
             tick, n_steps = -1, 0
             while max_steps is None or n_steps < max_steps:
-                a = self.actor.act(env.obs, eps=0.0, noisy=False)
-                info = env.step(a)[3]
+                info = env.step(act(env))[3]
                 if density is not None:
                     self.density_trace.append(env.probability(density, mean=True, mask=info["valid"])[0])
+                if wigner is not None:
+                    self.wigner_trace.append(env.wigner(wigner, mean=True, mask=info["valid"])[0])
                 n_steps += 1
                 prev, tick = tick, sched.tick(env, None)
                 if prev >= 0 and sched.poll(prev)["n"] >= episodes:
@@ -650,20 +664,24 @@ class Trainer:
                 f.write("{} +- {}\n".format(s["mean"], s["sem"]))
         return s["mean"], s["sem"], s["n"]
 
-    def _evaluate_performance(self, episodes: int, path: Optional[str], max_steps: Optional[int], density=None):
+    def _evaluate_performance(self, episodes: int, path: Optional[str], max_steps: Optional[int], density=None,
+                              wigner=None, act=None):
         """evaluate() with a monitor attached: the cooling drivers' --test statistic (QO/main_parallel.py:288-296,
         364-367), mean and sem of the episodes' performance, from a monitor made as the Trainer's with train = 0 that
         starts at the ring's end and receives once per control step; the stop condition counts its n."""
         mon = Monitor(device=self.monitor.device, **dict(self.monitor.params, train=0))
         env = self.env
+        if act is None:
+            act = lambda env: self.actor.act(env.obs, eps=0.0, noisy=False)   # noqa: E731
         try:
             mon.seek(env)
             call, n_steps = -1, 0
             while max_steps is None or n_steps < max_steps:
-                a = self.actor.act(env.obs, eps=0.0, noisy=False)
-                info = env.step(a)[3]
+                info = env.step(act(env))[3]
                 if density is not None:
                     self.density_trace.append(env.probability(density, mean=True, mask=info["valid"])[0])
+                if wigner is not None:
+                    self.wigner_trace.append(env.wigner(wigner, mean=True, mask=info["valid"])[0])
                 n_steps += 1
                 prev, call = call, mon.receive(env)
                 if prev >= 0 and mon.poll(prev)["n"] >= episodes:
@@ -702,7 +720,16 @@ def main(argv=None):
     ap.add_argument("--report_every", type=int, default=100)
     ap.add_argument("--density_out", metavar="PATH", default=None,
                     help="--test: x and the ensemble density per control step of the first model evaluated, one .npz")
+    ap.add_argument("--wigner_out", metavar="PATH", default=None,
+                    help="--test: x, p and the ensemble mean Wigner function per control step of the first model "
+                         "evaluated, one .npz")
+    ap.add_argument("--control_strategy", choices=("DQN", "LQG", "damping", "semiclassical"), default="DQN",
+                    help="other than DQN: one evaluation of the analytic baseline controller (ho / iho take LQG only, "
+                         "the drivers' --LQG)")
+    ap.add_argument("--con_parameter", type=float, default=0.9)
     args = ap.parse_args(argv)
+    if args.system in ("ho", "iho") and args.control_strategy not in ("DQN", "LQG"):
+        ap.error(f"--control_strategy {args.control_strategy}: the Fock systems take only DQN or LQG")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("train: one GPU only; WORLD_SIZE > 1 is refused (multi-GPU training is not built)")
 
@@ -714,13 +741,16 @@ def main(argv=None):
     fam = {"ho": cfg.HO, "iho": cfg.IHO, "qo": cfg.QO, "iqo": cfg.IQO}[args.system]
     ph = cfg.DEFAULTS[fam]
     B, seed = args.envs, args.seed
+    training = not args.test and args.control_strategy == "DQN"
     env_kw, monitor = {}, None
     if fam in (cfg.HO, cfg.QO):
         # the cooling drivers are measured and saved by the episodes' performance (receive_net)
         env_kw["performance_from"] = performance_from(ph, args.input)
         train_cutoff = 12.      # QO/arguments.py: --energy_cutoff
         if fam == cfg.QO:
-            env_kw["energy_cutoff"] = args.test_energy_cutoff if args.test else train_cutoff   # QO/main_parallel.py:206
+            # QO/main_parallel.py:206: args.energy_cutoff if args.train else args.test_energy_cutoff; a baseline run
+            # is not a training run (QO/arguments.py:99), so it is judged at the test cutoff like --test
+            env_kw["energy_cutoff"] = train_cutoff if training else args.test_energy_cutoff
         monitor = Monitor.for_driver(ph, num_of_saves=args.num_of_saves, energy_cutoff=train_cutoff)
     env = BatchedEnv(ph, B, 0, seed=seed, input=args.input, reset="warmup" if fam == cfg.QO else "deferred", **env_kw)
     # the drivers' learner table: fc2's width, the TD target, LaProp's betas
@@ -730,7 +760,7 @@ def main(argv=None):
     schedule = Schedule.for_driver(ph, batch_size=args.batch_size, n_times_per_sample=args.n_times_per_sample,
                                    train_episodes_multiplicative=args.train_episodes_multiplicative,
                                    init_lr=args.init_lr, t_max=env.t_max,
-                                   max_updates_per_tick=args.max_updates_per_tick, train=not args.test)
+                                   max_updates_per_tick=args.max_updates_per_tick, train=training)
     kw = dict(batch_size=args.batch_size, lr=schedule.params["lr_init"], target=target, betas=betas, device=0,
               seed=seed + 4)
     if fam == cfg.QO:
@@ -755,23 +785,49 @@ def main(argv=None):
         trainer.load_checkpoint(args.resume)
     else:
         env.reset()
-    if args.test:
+    baseline = args.control_strategy != "DQN"
+    if args.test or baseline:
+        import numpy as np
         n_test = args.num_of_test_episodes or {cfg.IHO: 4000, cfg.IQO: 4000, cfg.HO: 500, cfg.QO: 300}[fam]
-        folder = args.load_dir or args.save_dir
-        names = sorted((f for f in os.listdir(folder) if f.endswith(".pth")), key=lambda f: int(f[:-4]))
-        view = None
+        view = wview = None
         if args.density_out:
             from .spatial import SpatialView
             view = SpatialView.for_physics(ph)
+        if args.wigner_out:
+            from .wigner import WignerView
+            wview = WignerView.for_physics(ph)
+
+        def write_traces():
+            if view is not None:
+                np.savez(args.density_out, x=view.x.cpu().numpy(),
+                         density=torch.stack(trainer.density_trace).cpu().numpy())
+            if wview is not None:
+                np.savez(args.wigner_out, x=wview.x.cpu().numpy(), p=wview.p.cpu().numpy(),
+                         wigner=torch.stack(trainer.wigner_trace).cpu().numpy())
+
+        if baseline:
+            # the reference's file name: 'LQG' (IHO/main_parallel.py:610-612), 'semiclassical', or the strategy with
+            # str(con_parameter) (QO/main_parallel.py:534-537)
+            if ph.fock or args.control_strategy == "semiclassical":
+                name = args.control_strategy
+            else:
+                name = args.control_strategy + str(args.con_parameter)
+            os.makedirs(args.save_dir, exist_ok=True)
+            mean, sem, n = trainer.evaluate(None, n_test, path=os.path.join(args.save_dir, name + ".txt"),
+                                            max_steps=args.max_steps, density=view, wigner=wview,
+                                            controller=(args.control_strategy, args.con_parameter))
+            print(f"{name}: {mean} +- {sem} ({n} episodes)", flush=True)
+            write_traces()
+            return 0
+        folder = args.load_dir or args.save_dir
+        names = sorted((f for f in os.listdir(folder) if f.endswith(".pth")), key=lambda f: int(f[:-4]))
         for i, name in enumerate(names):
             model = torch.load(os.path.join(folder, name), map_location="cuda", weights_only=True)
             mean, sem, n = trainer.evaluate(model, n_test, path=os.path.join(folder, name[:-4] + ".txt"),
-                                            density=view if i == 0 else None)
+                                            density=view if i == 0 else None, wigner=wview if i == 0 else None)
             print(f"{name}: {mean} +- {sem} ({n} episodes)", flush=True)
-            if view is not None and i == 0:
-                import numpy as np
-                np.savez(args.density_out, x=view.x.cpu().numpy(),
-                         density=torch.stack(trainer.density_trace).cpu().numpy())
+            if i == 0:
+                write_traces()
         return 0
     steps = trainer.run(args.max_steps, report_every=args.report_every)
     s = trainer.schedule.stats()

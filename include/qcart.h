@@ -881,6 +881,42 @@ int qc_spatial_probability(qc_spatial* s, const void* psi, int32_t B, int32_t n_
 int qc_spatial_mean(qc_spatial* s, const void* psi, int32_t B, int32_t n_state, const uint8_t* mask, double threshold,
                     double* out, int64_t* count);
 
+/* ---- phase-space view: the Wigner function of a batch of wavefunctions on the device --------------------------------
+ * For a wavefunction phi sampled on a uniform grid (phi_i = phi(x_0 + i h), sum_i h |phi_i|^2 = 1) and momenta p[P]:
+ *   K_i = min(i, x_n - 1 - i),  c_ik = conj(phi_{i+k}) phi_{i-k},
+ *   W[i][j] = (h / pi) ( |phi_i|^2 + 2 sum_{k = 1 .. K_i} ( Re c_ik cos(2 p_j k h) - Im c_ik sin(2 p_j k h) ) ),
+ * which is (1 / pi) int conj(phi(x + y)) phi(x - y) e^{2 i p y} dy with hbar = 1, y = k h and phi = 0 off the grid: a
+ * packet e^{+i p0 x} sits at p = +p0. x_n in [1, 4096], h finite and > 0, P in [1, 1024], every p finite with
+ * |p_j| h <= pi (one period of the grid's momentum); anything else is refused with a text. The table
+ * (cos, sin)(2 p_j h k), k = 1 .. (x_n - 1) / 2, is built on the host at create time in long double and rounded once
+ * to fp64 (csrc/qcart_wigner.hpp): each entry within 2^-53 + 2^-62 |a| of the cos / sin of the exact a = 2 p_j h k.
+ * phi is [B][x_n] complex128 on the device (for Fock states: qc_spatial_repr's output on the same grid).
+ * qc_wigner_eval writes W [B][x_n][P] (64-bit offsets); W[b] does not depend on B or on where env b sits. An element
+ * is fl(s * acc), s = fl(2 h / pi), acc the fp64 matrix pipe's sum over the lags in ascending steps of four, lag 0
+ * entering with the weight 1/2.
+ * qc_wigner_mean: m[i][j] = (sum over the envs b with mask[b] != 0 (mask NULL: all) of W[b][i][j]) / count, and count
+ * itself; count == 0 gives zeros. No per-env W is written: the env index is one more index of the contraction. The
+ * order of the sum is fixed by (B, x_n, P) alone: the envs form chunks of E = qc_wigner_chunk(x_n) consecutive envs
+ * (2 for x_n <= 512, else 1; envs past B and masked envs enter as zero operands); there are
+ * S = qc_wigner_splits(B, x_n, P) = min(ceil(B / E), 256, max(1, 2^23 / (x_n P))) splits, split s owns the chunks s,
+ * s + S, s + 2 S, ..; its accumulator runs, from +0, over its chunks in that order, within a chunk over the lags in
+ * ascending steps of four, within a step over the chunk's envs in ascending order; then t = the running sum, from +0,
+ * of the splits' accumulators 0, 1, .., S - 1 and m = fl(fl(s * t) / (double)count). No atomics. The splits'
+ * accumulators live in a buffer the handle owns, made at create time for the largest S (at most 64 MiB): no call
+ * allocates or waits. All calls are asynchronous on the bound stream. */
+typedef struct qc_wigner qc_wigner;
+int qc_wigner_create(int32_t x_n, double h, const double* p /* host [P] */, int32_t P, int device, qc_wigner** out);
+void qc_wigner_destroy(qc_wigner* w);
+const char* qc_wigner_last_error(const qc_wigner* w);
+int qc_wigner_set_stream(qc_wigner* w, void* stream);
+/* phi: device [B][x_n] complex128; out: device [B][x_n][P] */
+int qc_wigner_eval(qc_wigner* w, const void* phi, int32_t B, double* out);
+/* mask: device uint8 [B] or NULL; out: device [x_n][P]; count: device, may be NULL */
+int qc_wigner_mean(qc_wigner* w, const void* phi, int32_t B, const uint8_t* mask, double* out, int64_t* count);
+/* the mean's order (above): envs per chunk, and the number of splits (0 for arguments out of range) */
+int qc_wigner_chunk(int32_t x_n);
+int qc_wigner_splits(int32_t B, int32_t x_n, int32_t P);
+
 /* ---- step server: the reference's process model on one GPU ------------------------------------------------
  * The drivers run 30-40 actor processes, each with its own `simulation` module stepping ONE env per call
  * (IHO/main_parallel.py:345-359, :264). A step server owns one handle of batch max_clients (env e = client slot
