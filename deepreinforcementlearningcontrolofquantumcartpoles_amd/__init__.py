@@ -10,12 +10,13 @@ Modules:
   learner     DQNLearner / MeasurementLearner: the reference's TrainDQN update on the device
   spatial     SpatialView: the drivers' spatial_repr / probability (position-space density) of a batch of states
   wigner      WignerView: the Wigner function (phase-space view) of a batch of states and its ensemble mean
+  ensemble    EnsembleView: the ensemble density matrix of a batch of states; purity, populations, fidelity
   checkpoint  save / load of the whole device loop; the resumed run is the uninterrupted one bit for bit
 """
 from .config import DEFAULTS, HO, IHO, IQO, QO, Physics  # noqa: F401
 
 __all__ = ["DEFAULTS", "HO", "IHO", "QO", "IQO", "Physics", "DQNLearner", "MeasurementLearner", "SpatialView",
-           "WignerView"]
+           "WignerView", "EnsembleView"]
 
 
 def __getattr__(name):
@@ -29,4 +30,7 @@ def __getattr__(name):
     if name == "WignerView":
         from . import wigner
         return wigner.WignerView
+    if name == "EnsembleView":
+        from . import ensemble
+        return ensemble.EnsembleView
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -57,6 +57,8 @@ EXPORTS = (
     "qc_spatial_repr", "qc_spatial_probability", "qc_spatial_mean",
     "qc_wigner_create", "qc_wigner_destroy", "qc_wigner_last_error", "qc_wigner_set_stream", "qc_wigner_eval",
     "qc_wigner_mean", "qc_wigner_chunk", "qc_wigner_splits",
+    "qc_ensemble_create", "qc_ensemble_destroy", "qc_ensemble_last_error", "qc_ensemble_set_stream",
+    "qc_ensemble_density", "qc_ensemble_chunk", "qc_ensemble_splits",
 ) + tuple(f"qc_{kind}_state_{op}" for kind in ("actor", "mactor", "replay", "learner", "mlearner", "sched", "monitor")
           for op in ("bytes", "export", "import"))   # checkpoint: a handle's whole state as one host buffer
 
@@ -523,6 +525,15 @@ def lib() -> ctypes.CDLL:
     L.qc_wigner_mean.argtypes = [vp, vp, i32, vp, vp, vp]
     L.qc_wigner_chunk.argtypes = [i32]
     L.qc_wigner_splits.argtypes = [i32, i32, i32]
+    L.qc_ensemble_create.argtypes = [i32, d, ctypes.c_int, P(vp)]
+    L.qc_ensemble_destroy.argtypes = [vp]
+    L.qc_ensemble_destroy.restype = None
+    L.qc_ensemble_last_error.argtypes = [vp]
+    L.qc_ensemble_last_error.restype = ctypes.c_char_p
+    L.qc_ensemble_set_stream.argtypes = [vp, vp]
+    L.qc_ensemble_density.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.qc_ensemble_chunk.argtypes = [i32]
+    L.qc_ensemble_splits.argtypes = [i32, i32]
     L.qc_mlearner_stats.argtypes = [vp, P(QcLearnerStats)]
     L.qc_mlearner_grads.argtypes = [vp, P(QcDqnLayer)]
     L.qc_mlearner_apply.argtypes = [vp, P(QcDqnLayer)]
@@ -579,6 +590,7 @@ check_sched = _checker("qc_sched")
 check_monitor = _checker("qc_monitor")
 check_spatial = _checker("qc_spatial")
 check_wigner = _checker("qc_wigner")
+check_ensemble = _checker("qc_ensemble")
 
 
 class DeviceHandle:

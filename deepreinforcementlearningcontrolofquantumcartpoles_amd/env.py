@@ -654,6 +654,12 @@ class BatchedEnv:
             raise ValueError("BatchedEnv.wigner: mask goes with mean = True")
         return view.wigner(self.psi)
 
+    def density_matrix(self, view, mask: Optional[torch.Tensor] = None):
+        """The ensemble density matrix of the current states through an ensemble.EnsembleView made for this physics
+        (EnsembleView.for_physics): `view.density_matrix(self.psi, mask)`, the pair (rho [N, N], count) over the envs
+        whose mask is set. Reads psi only: the env's state is unchanged."""
+        return view.density_matrix(self.psi, mask)
+
     @staticmethod
     def experience(last_obs: torch.Tensor, obs: torch.Tensor, action: torch.Tensor, reward: torch.Tensor):
         """Experience rows in the reference layout np.hstack((last_data, data, [last_action], [reward]))."""

@@ -613,7 +613,7 @@ class Trainer:
     # ------------------------------------------------------------------ --test
     def evaluate(self, params: Optional[Mapping[str, torch.Tensor]], episodes: int, path: Optional[str] = None,
                  max_steps: Optional[int] = None, density=None, wigner=None,
-                 controller: Optional[tuple] = None):
+                 controller: Optional[tuple] = None, ensemble=None, rho_every: int = 0):
         """The drivers' --test mode (IHO/main_parallel.py:367-377, 442-445): `params` (a state_dict; None: the
         actor's current weights) act greedily without parameter noise (eps = 0, noisy = False: net.eval(),
         layers.py:40) under a schedule made as this one with train = 0, until at least `episodes` episodes have
@@ -624,7 +624,11 @@ class Trainer:
         position-space density of the envs that were live at that step (info['valid']) to `self.density_trace`, a
         list of device [X] tensors that starts empty with each call; nothing in the loop waits for them and the
         returned tuple is the same. `wigner` (a wigner.WignerView for the env's physics) does the same with the
-        ensemble mean Wigner function, [X, P] tensors in `self.wigner_trace`.
+        ensemble mean Wigner function, [X, P] tensors in `self.wigner_trace`. `ensemble` (an ensemble.EnsembleView for
+        the env's physics) takes the density matrix rho of the live envs once per control step and appends its purity
+        (a 0-d tensor) to `self.purity_trace` and its populations ([N]) to `self.population_trace`; with
+        rho_every = k > 0 the full rho of the control steps 0, k, 2 k, .. goes to `self.rho_trace` and their indices to
+        `self.rho_steps` (a full rho per step at 521 points over an evaluation is gigabytes: it is opt-in).
         `controller` = (strategy, con_parameter): the drivers' baseline runs (--control_strategy / --con_parameter,
         QO/main_parallel.py:166-176; --LQG, IHO/main_parallel.py:194-206): the actions come from
         env.analytic_actions(strategy, con_parameter) and the actor is not touched; `params` must be None."""
@@ -639,8 +643,14 @@ class Trainer:
             act = lambda env: self.actor.act(env.obs, eps=0.0, noisy=False)   # noqa: E731
         self.density_trace: list = []
         self.wigner_trace: list = []
+        self.purity_trace: list = []
+        self.population_trace: list = []
+        self.rho_trace: list = []
+        self.rho_steps: list = []
+        if rho_every < 0:
+            raise ValueError("Trainer.evaluate: rho_every must be >= 0")
         if self.monitor is not None:
-            return self._evaluate_performance(episodes, path, max_steps, density, wigner, act)
+            return self._evaluate_performance(episodes, path, max_steps, density, wigner, act, ensemble, rho_every)
         sched = Schedule(device=self.schedule.device, **dict(self.schedule.params, train=0))
         env = self.env
         try:
@@ -652,6 +662,8 @@ class Trainer:
                     self.density_trace.append(env.probability(density, mean=True, mask=info["valid"])[0])
                 if wigner is not None:
                     self.wigner_trace.append(env.wigner(wigner, mean=True, mask=info["valid"])[0])
+                if ensemble is not None:
+                    self._record_rho(ensemble, rho_every, info["valid"], n_steps)
                 n_steps += 1
                 prev, tick = tick, sched.tick(env, None)
                 if prev >= 0 and sched.poll(prev)["n"] >= episodes:
@@ -664,8 +676,17 @@ class Trainer:
                 f.write("{} +- {}\n".format(s["mean"], s["sem"]))
         return s["mean"], s["sem"], s["n"]
 
+    def _record_rho(self, ensemble, rho_every: int, valid, step: int):
+        """One control step's entries of evaluate(ensemble=...): asynchronous, nothing waits."""
+        rho = self.env.density_matrix(ensemble, mask=valid)[0]
+        self.purity_trace.append(ensemble.purity(rho))
+        self.population_trace.append(ensemble.populations(rho))
+        if rho_every > 0 and step % rho_every == 0:
+            self.rho_trace.append(rho)
+            self.rho_steps.append(step)
+
     def _evaluate_performance(self, episodes: int, path: Optional[str], max_steps: Optional[int], density=None,
-                              wigner=None, act=None):
+                              wigner=None, act=None, ensemble=None, rho_every: int = 0):
         """evaluate() with a monitor attached: the cooling drivers' --test statistic (QO/main_parallel.py:288-296,
         364-367), mean and sem of the episodes' performance, from a monitor made as the Trainer's with train = 0 that
         starts at the ring's end and receives once per control step; the stop condition counts its n."""
@@ -682,6 +703,8 @@ class Trainer:
                     self.density_trace.append(env.probability(density, mean=True, mask=info["valid"])[0])
                 if wigner is not None:
                     self.wigner_trace.append(env.wigner(wigner, mean=True, mask=info["valid"])[0])
+                if ensemble is not None:
+                    self._record_rho(ensemble, rho_every, info["valid"], n_steps)
                 n_steps += 1
                 prev, call = call, mon.receive(env)
                 if prev >= 0 and mon.poll(prev)["n"] >= episodes:
@@ -723,6 +746,10 @@ def main(argv=None):
     ap.add_argument("--wigner_out", metavar="PATH", default=None,
                     help="--test: x, p and the ensemble mean Wigner function per control step of the first model "
                          "evaluated, one .npz")
+    ap.add_argument("--rho_out", metavar="PATH", default=None,
+                    help="--test: purity and populations of the ensemble density matrix per control step of the first "
+                         "model evaluated (with --rho_every K > 0 also rho and rho_steps of every K-th step), one .npz")
+    ap.add_argument("--rho_every", type=int, default=0)
     ap.add_argument("--control_strategy", choices=("DQN", "LQG", "damping", "semiclassical"), default="DQN",
                     help="other than DQN: one evaluation of the analytic baseline controller (ho / iho take LQG only, "
                          "the drivers' --LQG)")
@@ -789,13 +816,16 @@ def main(argv=None):
     if args.test or baseline:
         import numpy as np
         n_test = args.num_of_test_episodes or {cfg.IHO: 4000, cfg.IQO: 4000, cfg.HO: 500, cfg.QO: 300}[fam]
-        view = wview = None
+        view = wview = eview = None
         if args.density_out:
             from .spatial import SpatialView
             view = SpatialView.for_physics(ph)
         if args.wigner_out:
             from .wigner import WignerView
             wview = WignerView.for_physics(ph)
+        if args.rho_out:
+            from .ensemble import EnsembleView
+            eview = EnsembleView.for_physics(ph)
 
         def write_traces():
             if view is not None:
@@ -804,6 +834,13 @@ def main(argv=None):
             if wview is not None:
                 np.savez(args.wigner_out, x=wview.x.cpu().numpy(), p=wview.p.cpu().numpy(),
                          wigner=torch.stack(trainer.wigner_trace).cpu().numpy())
+            if eview is not None:
+                out = dict(purity=torch.stack(trainer.purity_trace).cpu().numpy(),
+                           populations=torch.stack(trainer.population_trace).cpu().numpy())
+                if args.rho_every > 0:
+                    out.update(rho=torch.stack(trainer.rho_trace).cpu().numpy(),
+                               rho_steps=np.array(trainer.rho_steps, dtype=np.int64))
+                np.savez(args.rho_out, **out)
 
         if baseline:
             # the reference's file name: 'LQG' (IHO/main_parallel.py:610-612), 'semiclassical', or the strategy with
@@ -815,7 +852,8 @@ def main(argv=None):
             os.makedirs(args.save_dir, exist_ok=True)
             mean, sem, n = trainer.evaluate(None, n_test, path=os.path.join(args.save_dir, name + ".txt"),
                                             max_steps=args.max_steps, density=view, wigner=wview,
-                                            controller=(args.control_strategy, args.con_parameter))
+                                            controller=(args.control_strategy, args.con_parameter),
+                                            ensemble=eview, rho_every=args.rho_every)
             print(f"{name}: {mean} +- {sem} ({n} episodes)", flush=True)
             write_traces()
             return 0
@@ -824,7 +862,8 @@ def main(argv=None):
         for i, name in enumerate(names):
             model = torch.load(os.path.join(folder, name), map_location="cuda", weights_only=True)
             mean, sem, n = trainer.evaluate(model, n_test, path=os.path.join(folder, name[:-4] + ".txt"),
-                                            density=view if i == 0 else None, wigner=wview if i == 0 else None)
+                                            density=view if i == 0 else None, wigner=wview if i == 0 else None,
+                                            ensemble=eview if i == 0 else None, rho_every=args.rho_every)
             print(f"{name}: {mean} +- {sem} ({n} episodes)", flush=True)
             if i == 0:
                 write_traces()

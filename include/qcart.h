@@ -917,6 +917,42 @@ int qc_wigner_mean(qc_wigner* w, const void* phi, int32_t B, const uint8_t* mask
 int qc_wigner_chunk(int32_t x_n);
 int qc_wigner_splits(int32_t B, int32_t x_n, int32_t P);
 
+/* ---- ensemble view: the density matrix of a batch of states on the device -------------------------------------------
+ * For states psi [B][N] complex128 (contiguous, on the device), N in [1, 2048]:
+ *   t[m][n]   = sum over the envs b with mask[b] != 0 (mask NULL: all) of psi_b[m] * conj(psi_b[n]),
+ *   rho[m][n] = fl( fl(scale * t[m][n]) / count ),   count = the number of set mask bytes (no mask: B),
+ * the unconditional state of the ensemble. scale is a positive finite double fixed at create time: 1 for Fock states,
+ * the grid spacing h for the grid families' continuum-normalised states (sum h |psi|^2 = 1). The states are not
+ * renormalised: Tr rho is the mean of scale * ||psi_b||^2 over the live envs, which is 1 for normalised states. count
+ * is written as one int64 on the device; with count == 0 every element is zero and nothing is divided. A masked env,
+ * and the env past B that pads an odd B's last chunk, is a row of exact zeros as an operand: zeros are selected for
+ * it, its memory (which may hold NaN or Inf) is never multiplied. N outside [1, 2048], a scale that is not finite and
+ * > 0, B < 1 and null pointers are refused with a text, the create arguments before the device is touched.
+ * The output is the full [N][N] complex128 matrix (row-major, rho[m][n] at m N + n) and is exactly Hermitian: only
+ * elements with n <= m are accumulated (64 x 32 blocks of 16 x 16 fp64 matrix-pipe tiles on or below the diagonal);
+ * the second stage writes rho[m][n] = (re, im) and rho[n][m] = (re, -im) from the same values (the sign bit flipped:
+ * -0.0 where im is +0.0), and +0.0 as the imaginary part of the diagonal, where the accumulation b a + (-a) b leaves
+ * a rounding residue.
+ * The order of the sum is fixed by (B, N) alone, never by the mask's content: the envs form chunks of
+ * E = qc_ensemble_chunk(N) = 2 consecutive envs (the K = 4 of one v_mfma_f64_16x16x4_f64 is 2 envs x (re, im));
+ * there are S = qc_ensemble_splits(B, N) = min(ceil(B / E), 256, max(1, floor(2^22 / N^2))) splits, split s owns the
+ * chunks s, s + S, s + 2 S, ..; its accumulators run, from +0, over its chunks in that order, one matrix instruction
+ * per chunk and tile; then t = the running sum, from +0, of the splits' accumulators 0, 1, .., S - 1, separately for
+ * the real and the imaginary part, and rho as above. No atomics. The splits' accumulators live in a buffer the handle
+ * owns, made at create time for the largest S ([S][2][N][N] doubles, at most 64 MiB): no call allocates or waits.
+ * All calls are asynchronous on the bound stream. */
+typedef struct qc_ensemble qc_ensemble;
+int qc_ensemble_create(int32_t N, double scale, int device, qc_ensemble** out);
+void qc_ensemble_destroy(qc_ensemble* h);
+const char* qc_ensemble_last_error(const qc_ensemble* h);
+int qc_ensemble_set_stream(qc_ensemble* h, void* stream);
+/* psi: device [B][N] complex128; mask: device uint8 [B] or NULL; rho: device [N][N] complex128; count: device, may be
+ * NULL */
+int qc_ensemble_density(qc_ensemble* h, const void* psi, int32_t B, const uint8_t* mask, void* rho, int64_t* count);
+/* the order (above): envs per chunk, and the number of splits (0 for arguments out of range) */
+int qc_ensemble_chunk(int32_t N);
+int qc_ensemble_splits(int32_t B, int32_t N);
+
 /* ---- step server: the reference's process model on one GPU ------------------------------------------------
  * The drivers run 30-40 actor processes, each with its own `simulation` module stepping ONE env per call
  * (IHO/main_parallel.py:345-359, :264). A step server owns one handle of batch max_clients (env e = client slot
