@@ -1546,7 +1546,8 @@ __device__ __forceinline__ void step_body(const KArgs& a, const int32_t* order, 
     const bool win_on = a.win_hi > a.win_lo;
     // X psi carried across steps (Fock families; on the grid X is diagonal and recomputed per row)
     cx<RT> xp[FAM == 2 ? 1 : R];
-    if constexpr (FAM != 2) apply_x<FAM, R>(psi, xp, cf, lnv);
+    // (fp32: X psi and <x> are formed at the head of every step, from the rounded psi: below)
+    if constexpr (FAM != 2 && sizeof(RT) == 8) apply_x<FAM, R>(psi, xp, cf, lnv);
     // grid: H_F's diagonal with the slot's force folded in, once per call (MODE 0: registers; MODE >= 1:
     // the block's LDS image, RowLds)
     constexpr bool RCL = FAM == 2 && MODE >= 1 && grid_rows_in_lds(R);
@@ -1571,9 +1572,9 @@ __device__ __forceinline__ void step_body(const KArgs& a, const int32_t* order, 
             return 0;
         }
     };
-    RT xbar;
+    RT xbar = RT(0);
     int term = -1, fail = 0;
-    {
+    if constexpr (sizeof(RT) == 8) {
         double s[2] = {0.0, 0.0};
 #pragma unroll
         for (int j = 0; j < R; ++j) {
@@ -1637,6 +1638,17 @@ __device__ __forceinline__ void step_body(const KArgs& a, const int32_t* order, 
         // 2 774 instructions). The fp32 R = 32 kernel (C5) too (round 5: SGPR-spill lane moves 402 -> 112 per
         // step, 42.5 -> 41.9 ms, same call); not the grid R = 17 kernel (C3: 156.8 -> 159.5 ms, same call)
         const auto& a = step_kargs<KAR>(a_in);   // (shadows the parameter inside the step)
+        if constexpr (!LAZY) {
+            // fp32: psi is rounded where a step normalises it, and every step forms its X psi and <x> from that
+            // rounded psi, the first step of a call and a later one by these same expressions: a call that ends
+            // after n steps and one that goes on take the same next step bit for bit (n + m steps = two calls)
+            apply_x<FAM, R>(psi, xp, cf, lnv);
+            double t[2] = {0.0, 0.0};
+#pragma unroll
+            for (int j = 0; j < R; ++j) t[0] += (double)(psi[j].re * xp[j].re + psi[j].im * xp[j].im);
+            step_sum<2>(t, lnv);
+            xbar = (RT)(a.w * t[0]);
+        }
         const double dt = a.dt, sdt = a.sqrt_dt, g4 = a.g4, beta = a.beta;
         const double inv_sdt = HC ? a.inv_sdt : 1.0 / sdt, inv_dt = HC ? a.inv_dt : 1.0 / dt;
         const RT g4r = (RT)g4, dtr = (RT)dt, a5r = (RT)a.a5;
@@ -2160,7 +2172,7 @@ __device__ __forceinline__ void step_body(const KArgs& a, const int32_t* order, 
         // normalise (IHO:216-220, QO:259-263) + next <x> + Fail (IHO:422-426, QO:559-565) + IQO window
         {
             cx<RT> xn[R];
-            apply_x<FAM, R>(acc, xn, cf, lnv);
+            if constexpr (LAZY) apply_x<FAM, R>(acc, xn, cf, lnv);   // (fp32: at the head of the next step)
             // full reductions only for the norm and the next <x>; the boundary sums (Fail) touch the
             // few lanes holding the edge rows and are read from them directly
             double s[2] = {0.0, 0.0}, pwin = 0.0, stop = 0.0, sbot = 0.0;
@@ -2174,10 +2186,10 @@ __device__ __forceinline__ void step_body(const KArgs& a, const int32_t* order, 
 #pragma unroll
                 for (int j = R - 1; j >= 0; --j) {
                     s[0] = dot_acc(s[0], j == R - 1, acc[j], acc[j]);
-                    qx.add(j == R - 1, acc[j], xn[j]);
+                    if constexpr (LAZY) qx.add(j == R - 1, acc[j], xn[j]);
                     suf = fma(j == jt ? 1.0 : 0.0, s[0], suf);   // (0 / 1 weight: an FMA, not a lane select)
                 }
-                s[1] = qx.sum();
+                if constexpr (LAZY) s[1] = qx.sum();
                 const int l1 = (N - 1) / R;
                 if (lt < 64) stop = readlane_d(suf, lt);
                 for (int l = lt + 1; l <= l1 && l < 64; ++l) stop += readlane_d(s[0], l);
@@ -2205,7 +2217,7 @@ __device__ __forceinline__ void step_body(const KArgs& a, const int32_t* order, 
 #pragma unroll
             for (int j = 0; j < R; ++j) {   // LAZY: unnormalised (scl)
                 psi[j] = LAZY ? acc[j] : C(acc[j].re * (RT)scale, acc[j].im * (RT)scale);
-                xp[j] = LAZY ? xn[j] : C(xn[j].re * (RT)scale, xn[j].im * (RT)scale);
+                if constexpr (LAZY) xp[j] = xn[j];
             }
             if constexpr (LAZY) {
                 scl = scale;
@@ -2220,7 +2232,7 @@ __device__ __forceinline__ void step_body(const KArgs& a, const int32_t* order, 
                     sq = 1.0;
                 }
             }
-            xbar = (RT)(a.w * (s[1] * scale) * scale);
+            if constexpr (LAZY) xbar = (RT)(a.w * (s[1] * scale) * scale);
             // check_boundary_error: sqrt(sum |psi|^2) > thr, compared squared (no square roots)
             const double sc2 = scale * scale, thr2 = a.fail_thr * a.fail_thr;
             bool f = stop * sc2 > thr2;
