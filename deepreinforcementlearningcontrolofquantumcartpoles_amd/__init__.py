@@ -11,12 +11,13 @@ Modules:
   spatial     SpatialView: the drivers' spatial_repr / probability (position-space density) of a batch of states
   wigner      WignerView: the Wigner function (phase-space view) of a batch of states and its ensemble mean
   ensemble    EnsembleView: the ensemble density matrix of a batch of states; purity, populations, fidelity
+  levels      LevelView: eigenstates of the force-free Hamiltonian (host solve) and the level populations of a batch
   checkpoint  save / load of the whole device loop; the resumed run is the uninterrupted one bit for bit
 """
 from .config import DEFAULTS, HO, IHO, IQO, QO, Physics  # noqa: F401
 
 __all__ = ["DEFAULTS", "HO", "IHO", "QO", "IQO", "Physics", "DQNLearner", "MeasurementLearner", "SpatialView",
-           "WignerView", "EnsembleView"]
+           "WignerView", "EnsembleView", "LevelView"]
 
 
 def __getattr__(name):
@@ -33,4 +34,7 @@ def __getattr__(name):
     if name == "EnsembleView":
         from . import ensemble
         return ensemble.EnsembleView
+    if name == "LevelView":
+        from . import levels
+        return levels.LevelView
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -59,6 +59,8 @@ EXPORTS = (
     "qc_wigner_mean", "qc_wigner_chunk", "qc_wigner_splits",
     "qc_ensemble_create", "qc_ensemble_destroy", "qc_ensemble_last_error", "qc_ensemble_set_stream",
     "qc_ensemble_density", "qc_ensemble_chunk", "qc_ensemble_splits",
+    "qc_levels_solve", "qc_levels_create", "qc_levels_destroy", "qc_levels_last_error", "qc_levels_set_stream",
+    "qc_levels_amplitudes", "qc_levels_populations", "qc_levels_mean",
 ) + tuple(f"qc_{kind}_state_{op}" for kind in ("actor", "mactor", "replay", "learner", "mlearner", "sched", "monitor")
           for op in ("bytes", "export", "import"))   # checkpoint: a handle's whole state as one host buffer
 
@@ -534,6 +536,16 @@ def lib() -> ctypes.CDLL:
     L.qc_ensemble_density.argtypes = [vp, vp, i32, vp, vp, vp]
     L.qc_ensemble_chunk.argtypes = [i32]
     L.qc_ensemble_splits.argtypes = [i32, i32]
+    L.qc_levels_solve.argtypes = [P(QcParams), i32, vp, vp]
+    L.qc_levels_create.argtypes = [i32, i32, d, vp, ctypes.c_int, P(vp)]
+    L.qc_levels_destroy.argtypes = [vp]
+    L.qc_levels_destroy.restype = None
+    L.qc_levels_last_error.argtypes = [vp]
+    L.qc_levels_last_error.restype = ctypes.c_char_p
+    L.qc_levels_set_stream.argtypes = [vp, vp]
+    L.qc_levels_amplitudes.argtypes = [vp, vp, i32, vp]
+    L.qc_levels_populations.argtypes = [vp, vp, i32, vp]
+    L.qc_levels_mean.argtypes = [vp, vp, i32, vp, vp, vp]
     L.qc_mlearner_stats.argtypes = [vp, P(QcLearnerStats)]
     L.qc_mlearner_grads.argtypes = [vp, P(QcDqnLayer)]
     L.qc_mlearner_apply.argtypes = [vp, P(QcDqnLayer)]
@@ -591,6 +603,7 @@ check_monitor = _checker("qc_monitor")
 check_spatial = _checker("qc_spatial")
 check_wigner = _checker("qc_wigner")
 check_ensemble = _checker("qc_ensemble")
+check_levels = _checker("qc_levels")
 
 
 class DeviceHandle:

@@ -660,6 +660,17 @@ class BatchedEnv:
         whose mask is set. Reads psi only: the env's state is unchanged."""
         return view.density_matrix(self.psi, mask)
 
+    def level_populations(self, view, mean: bool = False, mask: Optional[torch.Tensor] = None):
+        """The energy-level populations of the current states through a levels.LevelView made for this physics
+        (LevelView.for_physics): `view.populations(self.psi)` [B, K], or with mean = True
+        `view.mean_populations(self.psi, mask)`, the pair (ensemble mean [K], count) over the envs whose mask is set.
+        Reads psi only: the env's state is unchanged."""
+        if mean:
+            return view.mean_populations(self.psi, mask)
+        if mask is not None:
+            raise ValueError("BatchedEnv.level_populations: mask goes with mean = True")
+        return view.populations(self.psi)
+
     @staticmethod
     def experience(last_obs: torch.Tensor, obs: torch.Tensor, action: torch.Tensor, reward: torch.Tensor):
         """Experience rows in the reference layout np.hstack((last_data, data, [last_action], [reward]))."""

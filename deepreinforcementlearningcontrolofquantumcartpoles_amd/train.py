@@ -613,7 +613,7 @@ class Trainer:
     # ------------------------------------------------------------------ --test
     def evaluate(self, params: Optional[Mapping[str, torch.Tensor]], episodes: int, path: Optional[str] = None,
                  max_steps: Optional[int] = None, density=None, wigner=None,
-                 controller: Optional[tuple] = None, ensemble=None, rho_every: int = 0):
+                 controller: Optional[tuple] = None, ensemble=None, rho_every: int = 0, levels=None):
         """The drivers' --test mode (IHO/main_parallel.py:367-377, 442-445): `params` (a state_dict; None: the
         actor's current weights) act greedily without parameter noise (eps = 0, noisy = False: net.eval(),
         layers.py:40) under a schedule made as this one with train = 0, until at least `episodes` episodes have
@@ -629,6 +629,8 @@ class Trainer:
         (a 0-d tensor) to `self.purity_trace` and its populations ([N]) to `self.population_trace`; with
         rho_every = k > 0 the full rho of the control steps 0, k, 2 k, .. goes to `self.rho_trace` and their indices to
         `self.rho_steps` (a full rho per step at 521 points over an evaluation is gigabytes: it is opt-in).
+        `levels` (a levels.LevelView for the env's physics): every control step appends the mean energy-level
+        populations [K] of the envs that were live at that step to `self.level_trace`, in the same manner.
         `controller` = (strategy, con_parameter): the drivers' baseline runs (--control_strategy / --con_parameter,
         QO/main_parallel.py:166-176; --LQG, IHO/main_parallel.py:194-206): the actions come from
         env.analytic_actions(strategy, con_parameter) and the actor is not touched; `params` must be None."""
@@ -647,10 +649,12 @@ class Trainer:
         self.population_trace: list = []
         self.rho_trace: list = []
         self.rho_steps: list = []
+        self.level_trace: list = []
         if rho_every < 0:
             raise ValueError("Trainer.evaluate: rho_every must be >= 0")
         if self.monitor is not None:
-            return self._evaluate_performance(episodes, path, max_steps, density, wigner, act, ensemble, rho_every)
+            return self._evaluate_performance(episodes, path, max_steps, density, wigner, act, ensemble, rho_every,
+                                              levels)
         sched = Schedule(device=self.schedule.device, **dict(self.schedule.params, train=0))
         env = self.env
         try:
@@ -664,6 +668,8 @@ class Trainer:
                     self.wigner_trace.append(env.wigner(wigner, mean=True, mask=info["valid"])[0])
                 if ensemble is not None:
                     self._record_rho(ensemble, rho_every, info["valid"], n_steps)
+                if levels is not None:
+                    self.level_trace.append(env.level_populations(levels, mean=True, mask=info["valid"])[0])
                 n_steps += 1
                 prev, tick = tick, sched.tick(env, None)
                 if prev >= 0 and sched.poll(prev)["n"] >= episodes:
@@ -686,7 +692,7 @@ class Trainer:
             self.rho_steps.append(step)
 
     def _evaluate_performance(self, episodes: int, path: Optional[str], max_steps: Optional[int], density=None,
-                              wigner=None, act=None, ensemble=None, rho_every: int = 0):
+                              wigner=None, act=None, ensemble=None, rho_every: int = 0, levels=None):
         """evaluate() with a monitor attached: the cooling drivers' --test statistic (QO/main_parallel.py:288-296,
         364-367), mean and sem of the episodes' performance, from a monitor made as the Trainer's with train = 0 that
         starts at the ring's end and receives once per control step; the stop condition counts its n."""
@@ -705,6 +711,8 @@ class Trainer:
                     self.wigner_trace.append(env.wigner(wigner, mean=True, mask=info["valid"])[0])
                 if ensemble is not None:
                     self._record_rho(ensemble, rho_every, info["valid"], n_steps)
+                if levels is not None:
+                    self.level_trace.append(env.level_populations(levels, mean=True, mask=info["valid"])[0])
                 n_steps += 1
                 prev, call = call, mon.receive(env)
                 if prev >= 0 and mon.poll(prev)["n"] >= episodes:
@@ -750,6 +758,10 @@ def main(argv=None):
                     help="--test: purity and populations of the ensemble density matrix per control step of the first "
                          "model evaluated (with --rho_every K > 0 also rho and rho_steps of every K-th step), one .npz")
     ap.add_argument("--rho_every", type=int, default=0)
+    ap.add_argument("--levels_out", metavar="PATH", default=None,
+                    help="--test (ho / qo): energies [K] of the lowest --levels levels of the force-free Hamiltonian and "
+                         "the ensemble mean populations [T, K] per control step of the first model evaluated, one .npz")
+    ap.add_argument("--levels", type=int, default=32, metavar="K")
     ap.add_argument("--control_strategy", choices=("DQN", "LQG", "damping", "semiclassical"), default="DQN",
                     help="other than DQN: one evaluation of the analytic baseline controller (ho / iho take LQG only, "
                          "the drivers' --LQG)")
@@ -757,6 +769,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.system in ("ho", "iho") and args.control_strategy not in ("DQN", "LQG"):
         ap.error(f"--control_strategy {args.control_strategy}: the Fock systems take only DQN or LQG")
+    if args.levels_out and args.system in ("iho", "iqo"):
+        ap.error(f"--levels_out: --system {args.system} has no bound levels (H is not bounded below)")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("train: one GPU only; WORLD_SIZE > 1 is refused (multi-GPU training is not built)")
 
@@ -816,7 +830,7 @@ def main(argv=None):
     if args.test or baseline:
         import numpy as np
         n_test = args.num_of_test_episodes or {cfg.IHO: 4000, cfg.IQO: 4000, cfg.HO: 500, cfg.QO: 300}[fam]
-        view = wview = eview = None
+        view = wview = eview = lview = None
         if args.density_out:
             from .spatial import SpatialView
             view = SpatialView.for_physics(ph)
@@ -826,6 +840,9 @@ def main(argv=None):
         if args.rho_out:
             from .ensemble import EnsembleView
             eview = EnsembleView.for_physics(ph)
+        if args.levels_out:
+            from .levels import LevelView
+            lview = LevelView.for_physics(ph, args.levels)
 
         def write_traces():
             if view is not None:
@@ -841,6 +858,9 @@ def main(argv=None):
                     out.update(rho=torch.stack(trainer.rho_trace).cpu().numpy(),
                                rho_steps=np.array(trainer.rho_steps, dtype=np.int64))
                 np.savez(args.rho_out, **out)
+            if lview is not None:
+                np.savez(args.levels_out, energies=lview.energies.cpu().numpy(),
+                         populations=torch.stack(trainer.level_trace).cpu().numpy())
 
         if baseline:
             # the reference's file name: 'LQG' (IHO/main_parallel.py:610-612), 'semiclassical', or the strategy with
@@ -853,7 +873,7 @@ def main(argv=None):
             mean, sem, n = trainer.evaluate(None, n_test, path=os.path.join(args.save_dir, name + ".txt"),
                                             max_steps=args.max_steps, density=view, wigner=wview,
                                             controller=(args.control_strategy, args.con_parameter),
-                                            ensemble=eview, rho_every=args.rho_every)
+                                            ensemble=eview, rho_every=args.rho_every, levels=lview)
             print(f"{name}: {mean} +- {sem} ({n} episodes)", flush=True)
             write_traces()
             return 0
@@ -863,7 +883,8 @@ def main(argv=None):
             model = torch.load(os.path.join(folder, name), map_location="cuda", weights_only=True)
             mean, sem, n = trainer.evaluate(model, n_test, path=os.path.join(folder, name[:-4] + ".txt"),
                                             density=view if i == 0 else None, wigner=wview if i == 0 else None,
-                                            ensemble=eview if i == 0 else None, rho_every=args.rho_every)
+                                            ensemble=eview if i == 0 else None, rho_every=args.rho_every,
+                                            levels=lview if i == 0 else None)
             print(f"{name}: {mean} +- {sem} ({n} episodes)", flush=True)
             if i == 0:
                 write_traces()

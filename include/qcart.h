@@ -953,6 +953,53 @@ int qc_ensemble_density(qc_ensemble* h, const void* psi, int32_t B, const uint8_
 int qc_ensemble_chunk(int32_t N);
 int qc_ensemble_splits(int32_t B, int32_t N);
 
+/* ---- energy-level view: eigenstates of the force-free Hamiltonian, level populations of a batch of states ----------
+ * qc_levels_solve (host only; never touches a device): the lowest K eigenpairs of the real symmetric band H that the
+ * library builds for p's family and physics (HO: the diagonal omega (n + 1/2); QO: the 9-point kinetic stencil plus
+ * lambda x^4 on the grid). K in [1, min(N, 256)], N = the state length (qc_dim). energies[K] ascending; vectors[K][N],
+ * row k = level k with unit l2 norm, the last entry j with |V[k][j]| > 2^-26 max_j |V[k][j]| positive (the outermost
+ * lobe on the +x side, the convention of qc_spatial's table). Computed in long double (bisection on the band's
+ * inertia, inverse iteration, Rayleigh-quotient refinement; csrc/qcart_levels.hpp) and rounded once to fp64; the same
+ * bits on every call. HO: energies[k] is the band's diagonal entry bit for bit, vectors the identity exactly. IHO and
+ * IQO are refused ("no bound levels: H is not bounded below": their truncated matrices have edge-localised, pairwise
+ * near-degenerate lowest vectors; pass a table of your own to qc_levels_create instead). A level that does not
+ * converge, or two of the K levels closer than 2^-20 ||H||_inf, give QC_ESINGULAR, never garbage.
+ * qc_levels_create takes any real table V [K][N] (host; neither orthogonality nor norm is checked) and a scale:
+ * N in [1, 2048], K in [1, min(N, 256)], scale finite and > 0, every entry finite; anything else, B < 1 and null
+ * pointers are refused with a text, the create arguments before the device is touched. For the grid families'
+ * continuum-normalised states (sum h |psi|^2 = 1) and unit-norm rows, scale = sqrt(h) makes sum_k p[b][k] the in-band
+ * part of sum_j h |psi_b[j]|^2. psi is [B][N] complex128 (contiguous, on the device).
+ *   a[b][k] = ( fl(scale * s_re), fl(scale * s_im) ),  s_re = the fp64 matrix pipe's sum of V[k][j] * Re psi_b[j] over
+ *             j in ascending groups of four, from +0, one v_mfma_f64_16x16x4_f64 per group (the device table is padded
+ *             with zeros to whole groups), s_im the same over Im. a[b] does not depend on B or on where env b sits.
+ *   p[b][k] = fl( fl(re * re) + fl(im * im) ) of exactly that a[b][k].
+ *   m[k]    = (sum over the envs b with mask[b] != 0 (mask NULL: all) of p[b][k]) / count, and count itself;
+ *             count == 0 gives zeros and nothing is divided. No per-env p is written.
+ * The order of the mean's sum is fixed by (B, K, N) alone, never by the mask's content: the envs form groups of 64
+ * (group g = envs 64 g .. 64 g + 63), each of four sub-groups of 16 consecutive envs. A masked env, and an env past B,
+ * enters as a row of exact zero operands (zeros are selected for it by address; its memory, which may hold NaN or Inf,
+ * is never multiplied), so its p is +0. Within a sub-group s[q] (q = 0 .. 3) = the running sum, from +0, of p of the
+ * sub-group's envs q, q + 4, q + 8, q + 12 in that order, and the sub-group's sum is (s[0] + s[1]) + (s[2] + s[3]);
+ * the group's partial is (u[0] + u[1]) + (u[2] + u[3]) of its four sub-groups' sums; then the same rule once more:
+ * r[t] (t = 0 .. 3) = the running sum, from +0, of the partials of the groups t, t + 4, t + 8, .. in that order, and
+ * m[k] = ((r[0] + r[1]) + (r[2] + r[3])) / (double)count. Every operation is rounded once; no atomics. The partials
+ * live in a buffer the handle owns (it grows with B). All calls are asynchronous on the bound stream. */
+typedef struct qc_levels qc_levels;
+/* host only: energies host [K], vectors host [K][N] */
+int qc_levels_solve(const qc_params* p, int32_t K, double* energies, double* vectors);
+int qc_levels_create(int32_t N, int32_t K, double scale, const double* vectors /* host [K][N] */, int device,
+                     qc_levels** out);
+void qc_levels_destroy(qc_levels* h);
+/* h NULL: the text of the last failed qc_levels_solve / qc_levels_create */
+const char* qc_levels_last_error(const qc_levels* h);
+int qc_levels_set_stream(qc_levels* h, void* stream);
+/* psi: device [B][N] complex128; out: device [B][K] complex128 */
+int qc_levels_amplitudes(qc_levels* h, const void* psi, int32_t B, void* out);
+/* out: device [B][K] */
+int qc_levels_populations(qc_levels* h, const void* psi, int32_t B, double* out);
+/* mask: device uint8 [B] or NULL; out: device [K]; count: device, may be NULL */
+int qc_levels_mean(qc_levels* h, const void* psi, int32_t B, const uint8_t* mask, double* out, int64_t* count);
+
 /* ---- step server: the reference's process model on one GPU ------------------------------------------------
  * The drivers run 30-40 actor processes, each with its own `simulation` module stepping ONE env per call
  * (IHO/main_parallel.py:345-359, :264). A step server owns one handle of batch max_clients (env e = client slot
