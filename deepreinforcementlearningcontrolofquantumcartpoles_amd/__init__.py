@@ -12,12 +12,13 @@ Modules:
   wigner      WignerView: the Wigner function (phase-space view) of a batch of states and its ensemble mean
   ensemble    EnsembleView: the ensemble density matrix of a batch of states; purity, populations, fidelity
   levels      LevelView: eigenstates of the force-free Hamiltonian (host solve) and the level populations of a batch
+  lindblad    MasterEquation: the open-loop evolution of density matrices (the ensemble limit, the no-control curve)
   checkpoint  save / load of the whole device loop; the resumed run is the uninterrupted one bit for bit
 """
 from .config import DEFAULTS, HO, IHO, IQO, QO, Physics  # noqa: F401
 
 __all__ = ["DEFAULTS", "HO", "IHO", "QO", "IQO", "Physics", "DQNLearner", "MeasurementLearner", "SpatialView",
-           "WignerView", "EnsembleView", "LevelView"]
+           "WignerView", "EnsembleView", "LevelView", "MasterEquation"]
 
 
 def __getattr__(name):
@@ -37,4 +38,7 @@ def __getattr__(name):
     if name == "LevelView":
         from . import levels
         return levels.LevelView
+    if name == "MasterEquation":
+        from . import lindblad
+        return lindblad.MasterEquation
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

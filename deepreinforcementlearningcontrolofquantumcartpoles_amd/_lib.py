@@ -61,6 +61,9 @@ EXPORTS = (
     "qc_ensemble_density", "qc_ensemble_chunk", "qc_ensemble_splits",
     "qc_levels_solve", "qc_levels_create", "qc_levels_destroy", "qc_levels_last_error", "qc_levels_set_stream",
     "qc_levels_amplitudes", "qc_levels_populations", "qc_levels_mean",
+    "qc_lindblad_tables", "qc_lindblad_create", "qc_lindblad_destroy", "qc_lindblad_last_error",
+    "qc_lindblad_set_stream", "qc_lindblad_dim", "qc_lindblad_evolve", "qc_lindblad_congruence",
+    "qc_lindblad_take_errors",
 ) + tuple(f"qc_{kind}_state_{op}" for kind in ("actor", "mactor", "replay", "learner", "mlearner", "sched", "monitor")
           for op in ("bytes", "export", "import"))   # checkpoint: a handle's whole state as one host buffer
 
@@ -546,6 +549,17 @@ def lib() -> ctypes.CDLL:
     L.qc_levels_amplitudes.argtypes = [vp, vp, i32, vp]
     L.qc_levels_populations.argtypes = [vp, vp, i32, vp]
     L.qc_levels_mean.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.qc_lindblad_tables.argtypes = [P(QcParams), d, d, d, vp, vp, vp, vp, vp]
+    L.qc_lindblad_create.argtypes = [P(QcParams), d, d, vp, i32, ctypes.c_int, P(vp)]
+    L.qc_lindblad_destroy.argtypes = [vp]
+    L.qc_lindblad_destroy.restype = None
+    L.qc_lindblad_last_error.argtypes = [vp]
+    L.qc_lindblad_last_error.restype = ctypes.c_char_p
+    L.qc_lindblad_set_stream.argtypes = [vp, vp]
+    L.qc_lindblad_dim.argtypes = [vp]
+    L.qc_lindblad_evolve.argtypes = [vp, vp, i32, vp, i32, i32]
+    L.qc_lindblad_congruence.argtypes = [vp, vp, vp, vp, vp, i32]
+    L.qc_lindblad_take_errors.argtypes = [vp]
     L.qc_mlearner_stats.argtypes = [vp, P(QcLearnerStats)]
     L.qc_mlearner_grads.argtypes = [vp, P(QcDqnLayer)]
     L.qc_mlearner_apply.argtypes = [vp, P(QcDqnLayer)]
@@ -604,6 +618,7 @@ check_spatial = _checker("qc_spatial")
 check_wigner = _checker("qc_wigner")
 check_ensemble = _checker("qc_ensemble")
 check_levels = _checker("qc_levels")
+check_lindblad = _checker("qc_lindblad")
 
 
 class DeviceHandle:

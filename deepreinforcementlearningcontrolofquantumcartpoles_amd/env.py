@@ -671,6 +671,12 @@ class BatchedEnv:
             raise ValueError("BatchedEnv.level_populations: mask goes with mean = True")
         return view.populations(self.psi)
 
+    def master_equation(self, forces=None):
+        """A lindblad.MasterEquation for this env's physics, dt, gamma and device (forces None: the discrete forces,
+        slot = action): the open-loop evolution of density matrices. It never reads or writes the env's states."""
+        from .lindblad import MasterEquation
+        return MasterEquation(self.ph, forces, device=self.dev)
+
     @staticmethod
     def experience(last_obs: torch.Tensor, obs: torch.Tensor, action: torch.Tensor, reward: torch.Tensor):
         """Experience rows in the reference layout np.hstack((last_data, data, [last_action], [reward]))."""

@@ -682,6 +682,34 @@ class Trainer:
                 f.write("{} +- {}\n".format(s["mean"], s["sem"]))
         return s["mean"], s["sem"], s["n"]
 
+    def open_loop(self, me, n_control: int, slot: Optional[int] = None) -> dict:
+        """The no-control (fixed-force) curve of this loop: the ensemble density matrix of the env's current states
+        (through `me.ensemble`, the master equation's own ensemble.EnsembleView, which `me.close()` closes) evolved
+        `n_control` control intervals by the master equation `me` (lindblad.MasterEquation, env.master_equation())
+        at one slot (None: the F = 0 slot). Returns per-control-step traces [n_control + 1] (entry 0: the starting
+        rho) of 'trace', 'purity', 'x', 'x2', 'h', 'boundary' and, for the Fock families, 'n', as device tensors:
+        nothing is waited on, the env and whatever evaluate() returns are untouched."""
+        from .ensemble import EnsembleView
+        if isinstance(n_control, bool) or not isinstance(n_control, int) or n_control < 0:
+            raise ValueError("Trainer.open_loop: n_control must be an int >= 0")
+        env = self.env
+        rho = env.density_matrix(me.ensemble)[0]
+        names = ("x", "x2", "h") + (("n",) if env.ph.fock else ())
+        out: dict = {k: [] for k in ("trace", "purity", "boundary") + names}
+
+        def record():
+            out["trace"].append(torch.diagonal(rho).real.sum())
+            out["purity"].append(EnsembleView.purity(rho))
+            out["boundary"].append(me.boundary_weight(rho))
+            for k in names:
+                out[k].append(EnsembleView.expectation(rho, me.operator(k)).real)
+
+        record()
+        for _ in range(n_control):
+            me.evolve(rho, env.ci, slot)
+            record()
+        return {k: torch.stack(v) for k, v in out.items()}
+
     def _record_rho(self, ensemble, rho_every: int, valid, step: int):
         """One control step's entries of evaluate(ensemble=...): asynchronous, nothing waits."""
         rho = self.env.density_matrix(ensemble, mask=valid)[0]
@@ -762,6 +790,11 @@ def main(argv=None):
                     help="--test (ho / qo): energies [K] of the lowest --levels levels of the force-free Hamiltonian and "
                          "the ensemble mean populations [T, K] per control step of the first model evaluated, one .npz")
     ap.add_argument("--levels", type=int, default=32, metavar="K")
+    ap.add_argument("--open_loop_out", metavar="PATH", default=None,
+                    help="--test: the no-control curve of the driver, one .npz: the master equation's traces (trace, "
+                         "purity, x, x2, h, boundary; ho / iho also n) of the envs' starting ensemble over "
+                         "--open_loop_steps control intervals at zero force, and t")
+    ap.add_argument("--open_loop_steps", type=int, default=90, metavar="T")
     ap.add_argument("--control_strategy", choices=("DQN", "LQG", "damping", "semiclassical"), default="DQN",
                     help="other than DQN: one evaluation of the analytic baseline controller (ho / iho take LQG only, "
                          "the drivers' --LQG)")
@@ -843,6 +876,13 @@ def main(argv=None):
         if args.levels_out:
             from .levels import LevelView
             lview = LevelView.for_physics(ph, args.levels)
+        if args.open_loop_out:
+            # before the evaluation moves the envs; it reads their states only
+            me = env.master_equation()
+            curve = trainer.open_loop(me, args.open_loop_steps)
+            np.savez(args.open_loop_out, t=np.arange(args.open_loop_steps + 1) * (env.ci * ph.dt),
+                     **{k: v.cpu().numpy() for k, v in curve.items()})
+            me.close()
 
         def write_traces():
             if view is not None:

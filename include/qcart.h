@@ -1000,6 +1000,75 @@ int qc_levels_populations(qc_levels* h, const void* psi, int32_t B, double* out)
 /* mask: device uint8 [B] or NULL; out: device [K]; count: device, may be NULL */
 int qc_levels_mean(qc_levels* h, const void* psi, int32_t B, const uint8_t* mask, double* out, int64_t* count);
 
+/* ---- master equation: the open-loop evolution of density matrices --------------------------------------------------
+ * The average of the library's stochastic Schroedinger equation over the record, for a force F that does not depend
+ * on it, is closed:
+ *   d rho / dt = -i [H_F, rho] - (gamma / 4) [X, [X, rho]],   H_F = H - c F X
+ * (H, X, c as qc_create builds them for p's family and physics). The scheme works in the eigenbasis of the truncated
+ * position operator, X = W diag(xi) W^T (Fock families: W real orthogonal, xi ascending; grid families: W = I, xi the
+ * grid points), where the measurement term is elementwise. One step of length dt is the Strang composition
+ *   sigma <- G½ o sigma,  sigma <- T sigma T^†,  sigma <- G½ o sigma      (o: the elementwise product)
+ *   T = W^T C W,  C = (I + i dt/2 H_F)^-1 (I - i dt/2 H_F)   (the Cayley propagator of the step kernels' own matrix),
+ *   G½_ij = exp(-gamma dt (xi_i - xi_j)^2 / 8),  G_ij = exp(-gamma dt (xi_i - xi_j)^2 / 4),
+ * with the inner half-steps of consecutive steps merged:
+ *   evolve(rho, n):  sigma = W^T rho W (Fock only);  sigma <- G½ o sigma;
+ *                    n times: sigma <- g o (T sigma T^†), g = G, and G½ in the last repetition;
+ *                    rho = W sigma W^T (Fock only).
+ * C is unitary and G, G½ are positive-semidefinite kernels with a unit diagonal, so every step is an exact quantum
+ * channel: trace, Hermiticity and positivity hold up to rounding. Second order in dt; the reference's dt^3 .. dt^6
+ * drift corrections are deliberately absent (they would break the unitarity).
+ * qc_lindblad_tables (host only; never touches a device) gives the tables of one force, each computed in long double
+ * and rounded once to fp64 (csrc/qcart_lindblad.hpp): xi and W by qc_levels_solve's band solver on the tridiagonal X
+ * with K = N (the sign of column k by its convention; therefore Fock N <= 256), C by a partially pivoted complex band
+ * LU, T from the fp64 W, G and G½ by expl from the long double xi (the Rayleigh quotients of W's columns, whose rounding
+ * the returned xi is; G is not the square of the rounded G½; both symmetric with a unit diagonal exactly). Any output may be NULL. The same bits on every call. Fock N > 256, a grid outside
+ * [9, 2048] points, fp32 physics (precision == 1), a dt that is not finite and > 0, a gamma that is not finite and
+ * >= 0 and a force that is not finite are refused with a text.
+ * qc_lindblad_create builds the tables of J forces (slot s = forces[s]; J in [1, 32], J N^2 <= 2^25); its arguments
+ * are refused before the device is touched.
+ * The building block is the batched Hermitian congruence
+ *   Y_m = g o (A_s(m) X_m A_s(m)^†),  m < M,  X_m [N][N] complex128, A_s complex [N][N], g real symmetric or none,
+ * in two kernels on v_mfma_f64_16x16x4_f64: Z = A X (all of it), then Y = g o (Z A^†) for the elements on or below
+ * the diagonal only. The input is ASSUMED Hermitian and is not checked: the left product reads all of X as it
+ * stands, and the output is the exactly Hermitian matrix whose lower triangle is that of g o (A X A^†): Y[i][j] for
+ * j <= i and Y[j][i] = conj(Y[i][j]) are written from the same values (the sign bit of the imaginary part flipped),
+ * the diagonal's imaginary part is +0.0. y may equal x. M N^2 <= 2^27; Z lives in a buffer of the handle that grows
+ * with M (the only allocation any call makes).
+ * The order of every sum is a function of N alone. With a = A[i][k], x = X[k][j], the contraction index k runs in
+ * ascending groups of four from accumulators that start at +0, one matrix instruction per group and chain (rows,
+ * columns and k past N enter as exact zeros selected by address: what memory holds there, NaN or Inf included, is
+ * never multiplied), and per group the two accumulators of an element take their chains in this order:
+ *   Z:  re += x_re a_re;  re += (-x_im) a_im;  im += x_re a_im;  im += x_im a_re;
+ *   Y (z = Z[i][k], a = A[j][k]):  re += z_re a_re;  re += z_im a_im;  im += z_im a_re;  im += (-z_re) a_im;
+ * then Y = (fl(g_ij re), fl(g_ij im)), or (re, im) without g. Element (m, i, j) does not depend on M, on where X_m
+ * sits in the batch, or on which other matrices are in the call (a launch of fewer than 2048 blocks of 32 x 32 elements
+ * runs one 16 x 16 tile per workgroup instead of 2 x 2: that changes which workgroup computes an element, never its
+ * instructions or their order). No atomics; everything is asynchronous on the bound stream and nothing waits on the
+ * host.
+ * qc_lindblad_evolve works in place on rho [M][N][N] in the states' basis with qc_ensemble's normalisation
+ * (Tr rho = 1): 2 n_steps matrix launches and one elementwise launch, for Fock also the two basis changes (two
+ * congruences with the real W widened to a complex operand at create time). slots (device int32 [M]) picks the force
+ * of each rho; NULL: default_slot for all. A slot outside [0, J) leaves that rho untouched and raises the handle's
+ * device error flag: qc_lindblad_take_errors (synchronises, as qc_take_errors) reports it once. n_steps = 0 launches
+ * nothing and returns QC_OK. M < 1, n_steps < 0 and null pointers are refused with a text. */
+typedef struct qc_lindblad qc_lindblad;
+/* host only: xi host [N], W host [N][N] (grid: the identity), T host [N][N] complex128, g_half and g_full host [N][N] */
+int qc_lindblad_tables(const qc_params* p, double dt, double gamma, double force, double* xi, double* W, void* T,
+                       double* g_half, double* g_full);
+int qc_lindblad_create(const qc_params* p, double dt, double gamma, const double* forces /* host [J] */, int32_t J,
+                       int device, qc_lindblad** out);
+void qc_lindblad_destroy(qc_lindblad* h);
+/* h NULL: the text of the last failed qc_lindblad_tables / qc_lindblad_create */
+const char* qc_lindblad_last_error(const qc_lindblad* h);
+int qc_lindblad_set_stream(qc_lindblad* h, void* stream);
+int qc_lindblad_dim(const qc_lindblad* h);
+/* rho: device [M][N][N] complex128, in place; slots: device int32 [M] or NULL */
+int qc_lindblad_evolve(qc_lindblad* h, void* rho, int32_t M, const int32_t* slots, int32_t default_slot,
+                       int32_t n_steps);
+/* A: device [N][N] complex128; g: device [N][N] or NULL; x, y: device [M][N][N] complex128, y may equal x */
+int qc_lindblad_congruence(qc_lindblad* h, const void* A, const double* g, const void* x, void* y, int32_t M);
+int qc_lindblad_take_errors(qc_lindblad* h);
+
 /* ---- step server: the reference's process model on one GPU ------------------------------------------------
  * The drivers run 30-40 actor processes, each with its own `simulation` module stepping ONE env per call
  * (IHO/main_parallel.py:345-359, :264). A step server owns one handle of batch max_clients (env e = client slot
