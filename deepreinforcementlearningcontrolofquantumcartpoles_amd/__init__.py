@@ -8,8 +8,10 @@ Modules:
   env         BatchedEnv: reset/step/observation semantics of the reference drivers, batched
   distributed env sharding over ranks + RCCL gather of episode returns
   learner     DQNLearner / MeasurementLearner: the reference's TrainDQN update on the device
-  spatial     SpatialView: the drivers' spatial_repr / probability (position-space density) of a batch of states
-  wigner      WignerView: the Wigner function (phase-space view) of a batch of states and its ensemble mean
+  spatial     SpatialView: the drivers' spatial_repr / probability (position-space density) of a batch of states, and
+              the Fock -> position change of basis of density matrices
+  wigner      WignerView: the Wigner function (phase-space view) of a batch of states, its ensemble mean, and the
+              Wigner function and negative volume of density matrices
   ensemble    EnsembleView: the ensemble density matrix of a batch of states; purity, populations, fidelity
   levels      LevelView: eigenstates of the force-free Hamiltonian (host solve) and the level populations of a batch
   lindblad    MasterEquation: the open-loop evolution of density matrices (the ensemble limit, the no-control curve)

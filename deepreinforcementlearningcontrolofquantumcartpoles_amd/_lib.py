@@ -54,9 +54,9 @@ EXPORTS = (
     "qc_monitor_create", "qc_monitor_destroy", "qc_monitor_last_error", "qc_monitor_set_stream", "qc_monitor_receive",
     "qc_monitor_poll", "qc_monitor_seek", "qc_monitor_table",
     "qc_spatial_create", "qc_spatial_destroy", "qc_spatial_last_error", "qc_spatial_set_stream", "qc_spatial_table",
-    "qc_spatial_repr", "qc_spatial_probability", "qc_spatial_mean",
+    "qc_spatial_repr", "qc_spatial_probability", "qc_spatial_mean", "qc_spatial_congruence",
     "qc_wigner_create", "qc_wigner_destroy", "qc_wigner_last_error", "qc_wigner_set_stream", "qc_wigner_eval",
-    "qc_wigner_mean", "qc_wigner_chunk", "qc_wigner_splits",
+    "qc_wigner_mean", "qc_wigner_chunk", "qc_wigner_splits", "qc_wigner_eval_rho",
     "qc_ensemble_create", "qc_ensemble_destroy", "qc_ensemble_last_error", "qc_ensemble_set_stream",
     "qc_ensemble_density", "qc_ensemble_chunk", "qc_ensemble_splits",
     "qc_levels_solve", "qc_levels_create", "qc_levels_destroy", "qc_levels_last_error", "qc_levels_set_stream",
@@ -520,6 +520,7 @@ def lib() -> ctypes.CDLL:
     L.qc_spatial_repr.argtypes = [vp, vp, i32, i32, d, vp]
     L.qc_spatial_probability.argtypes = [vp, vp, i32, i32, d, vp]
     L.qc_spatial_mean.argtypes = [vp, vp, i32, i32, vp, d, vp, vp]
+    L.qc_spatial_congruence.argtypes = [vp, vp, i32, i32, d, vp]
     L.qc_wigner_create.argtypes = [i32, d, vp, i32, ctypes.c_int, P(vp)]
     L.qc_wigner_destroy.argtypes = [vp]
     L.qc_wigner_destroy.restype = None
@@ -528,6 +529,7 @@ def lib() -> ctypes.CDLL:
     L.qc_wigner_set_stream.argtypes = [vp, vp]
     L.qc_wigner_eval.argtypes = [vp, vp, i32, vp]
     L.qc_wigner_mean.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.qc_wigner_eval_rho.argtypes = [vp, vp, i32, vp]
     L.qc_wigner_chunk.argtypes = [i32]
     L.qc_wigner_splits.argtypes = [i32, i32, i32]
     L.qc_ensemble_create.argtypes = [i32, d, ctypes.c_int, P(vp)]

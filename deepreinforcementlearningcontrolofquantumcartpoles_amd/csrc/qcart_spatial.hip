@@ -22,6 +22,7 @@
 
 #include "../../include/qcart.h"
 #include "qcart_host.hpp"
+#include "qcart_phase.hpp"
 #include "qcart_spatial.hpp"
 
 namespace qcart {
@@ -288,6 +289,12 @@ struct qc_spatial {
     double* d_E = nullptr;      // [round_up(x_n, 256)][ldE], zero outside [x_n][n_levels]
     double* d_partial = nullptr;
     size_t partial_cap = 0;     // doubles
+    // qc_spatial_congruence (the kernels are qcart_phase.hip's)
+    int32_t ldX = 0;            // x_n rounded up to whole blocks of 256 points
+    double* d_Et = nullptr;     // the transposed table [ldE][ldX], d_Et[n][j] = E[j][n], zero outside [n_levels][x_n],
+                                // and one complex zero behind it: the operand of what does not enter
+    void* d_Z = nullptr;        // [z_cap][n_levels][x_n] complex128, of the largest M seen
+    size_t z_cap = 0;
 };
 
 namespace {
@@ -366,11 +373,19 @@ int qc_spatial_create(int32_t n_levels, const double* x, int32_t x_n, int device
     s->n_levels = n_levels;
     s->x_n = x_n;
     s->ldE = ldE;
+    s->ldX = rows;
     s->device = device;
     Dev g(device);
     if (n_levels > 0) {
+        std::vector<double> turned((size_t)ldE * (size_t)rows + 2, 0.);
+        for (int32_t j = 0; j < x_n; ++j)
+            for (int32_t n = 0; n < n_levels; ++n)
+                turned[(size_t)n * (size_t)rows + (size_t)j] = padded[(size_t)j * (size_t)ldE + (size_t)n];
         hipError_t e = hipMalloc((void**)&s->d_E, padded.size() * sizeof(double));
         if (e == hipSuccess) e = hipMemcpy(s->d_E, padded.data(), padded.size() * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) e = hipMalloc((void**)&s->d_Et, turned.size() * sizeof(double));
+        if (e == hipSuccess)
+            e = hipMemcpy(s->d_Et, turned.data(), turned.size() * sizeof(double), hipMemcpyHostToDevice);
         if (e != hipSuccess) {
             const std::string msg = std::string("qc_spatial_create: ") + hipGetErrorString(e);
             qc_spatial_destroy(s);
@@ -388,6 +403,8 @@ void qc_spatial_destroy(qc_spatial* s) {
         (void)hipDeviceSynchronize();
         if (s->d_E) (void)hipFree(s->d_E);
         if (s->d_partial) (void)hipFree(s->d_partial);
+        if (s->d_Et) (void)hipFree(s->d_Et);
+        if (s->d_Z) (void)hipFree(s->d_Z);
     }
     delete s;
 }
@@ -470,6 +487,34 @@ int qc_spatial_mean(qc_spatial* s, const void* psi, int32_t B, int32_t n_state, 
     hipLaunchKernelGGL(k_spatial_finish, dim3(1), dim3(kFinish), 0, s->stream, (const double*)s->d_partial, groups,
                        s->x_n, mask, B, out, count);
     return launched(s, "qc_spatial_mean");
+}
+
+int qc_spatial_congruence(qc_spatial* s, const void* rho, int32_t n_state, int32_t M, double scale, void* sigma) {
+    if (!s) return QC_EINVAL;
+    const std::string w = "qc_spatial_congruence: ";
+    if (s->n_levels == 0) return sfail(s, QC_EINVAL, w + "a grid view's density matrix lives on the grid already");
+    if (!rho || !sigma) return sfail(s, QC_EINVAL, w + "rho and sigma are required");
+    if (M < 1) return sfail(s, QC_EINVAL, w + "M must be >= 1");
+    if (n_state < 1 || n_state > s->n_levels)
+        return sfail(s, QC_EINVAL, w + "n_state must be in [1, n_levels = " + std::to_string(s->n_levels) + "], not " +
+                                       std::to_string(n_state));
+    if (!std::isfinite(scale)) return sfail(s, QC_EINVAL, w + "scale must be finite");
+    if ((int64_t)M * s->x_n * s->x_n > ((int64_t)1 << 27)) return sfail(s, QC_EINVAL, w + "M x_n^2 must be <= 2^27");
+    Dev g(s->device);
+    if ((size_t)M > s->z_cap) {
+        // (hipFree waits for the device: no launch still reads the old buffer)
+        if (s->d_Z) (void)hipFree(s->d_Z);
+        s->d_Z = nullptr;
+        s->z_cap = 0;
+        const size_t bytes = (size_t)M * (size_t)s->n_levels * (size_t)s->x_n * 2 * sizeof(double);
+        const hipError_t e = hipMalloc(&s->d_Z, bytes);
+        if (e != hipSuccess) return qcart::host::hip_fail(s->err, e, "qc_spatial_congruence");
+        s->z_cap = (size_t)M;
+    }
+    const double* zero = s->d_Et + (size_t)s->ldE * (size_t)s->ldX;
+    const hipError_t e = qcart::phase::launch_congruence(s->d_Et, s->ldX, zero, s->x_n, n_state, rho, M, scale, s->d_Z,
+                                                         sigma, s->stream);
+    return e == hipSuccess ? QC_OK : qcart::host::hip_fail(s->err, e, "qc_spatial_congruence");
 }
 
 }  // extern "C"

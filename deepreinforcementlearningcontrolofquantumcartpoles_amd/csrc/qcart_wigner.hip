@@ -29,15 +29,14 @@
 
 #include "../../include/qcart.h"
 #include "qcart_host.hpp"
+#include "qcart_phase.hpp"
 #include "qcart_wigner.hpp"
+#include "qcart_wigner_tiles.hpp"
 
 namespace qcart {
 namespace wigner {
 
 constexpr int kWave = 64;
-constexpr int kNT = 4;                 // column tiles per workgroup
-constexpr int kTP = 16 * kNT;          // momenta per workgroup
-constexpr int kStep = 4;               // lags per MFMA
 constexpr int kMaxSplits = 256;
 constexpr size_t kPartialCap = (size_t)1 << 23;   // doubles: the splits shrink so that the partials stay below this
 using f64x4 = double __attribute__((ext_vector_type(4)));
@@ -52,14 +51,6 @@ struct Args {
     double* partial;         // mean: [splits][X][P]
     int splits, chunks;      // mean: chunks = ceil(B / E); split s takes the chunks s, s + splits, ..
 };
-
-// the largest K_i = min(i, X - 1 - i) of the rows i0 .. min(i0 + 15, X - 1)
-__device__ __forceinline__ int tile_kmax(int i0, int X) {
-    const int n1 = X - 1, i1 = i0 + 15 < n1 ? i0 + 15 : n1, mid = n1 / 2;
-    const int a = i0 < n1 - i0 ? i0 : n1 - i0, b = i1 < n1 - i1 ? i1 : n1 - i1;
-    const int m = a > b ? a : b;
-    return i0 <= mid && mid <= i1 ? mid : m;
-}
 
 template <int E, bool MEAN>
 __device__ __forceinline__ void body(const Args& a) {
@@ -251,8 +242,8 @@ Args make_args(const qc_wigner* w, const void* phi, int32_t B) {
 }
 
 // the quads of position tiles and the groups of 64 momenta
-unsigned quads(int32_t X) { return (unsigned)((((X + 15) / 16 + 1) / 2 + 1) / 2); }
-unsigned groups(int32_t P) { return (unsigned)((P + kTP - 1) / kTP); }
+unsigned quads(int32_t X) { return tile_quads(X); }
+unsigned groups(int32_t P) { return momentum_groups(P); }
 
 int launched(qc_wigner* w, const char* who) {
     const hipError_t e = hipGetLastError();
@@ -365,6 +356,19 @@ int qc_wigner_mean(qc_wigner* w, const void* phi, int32_t B, const uint8_t* mask
     hipLaunchKernelGGL(k_wigner_finish, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, w->stream,
                        (const double*)w->d_partial, splits, n, w->scale, (const int64_t*)cnt, out);
     return launched(w, "qc_wigner_mean");
+}
+
+int qc_wigner_eval_rho(qc_wigner* w, const void* rho, int32_t M, double* out) {
+    if (!w) return QC_EINVAL;
+    const char* who = "qc_wigner_eval_rho";
+    if (!rho || !out) return wfail(w, QC_EINVAL, std::string(who) + ": rho and out are required");
+    if (M < 1) return wfail(w, QC_EINVAL, std::string(who) + ": M must be >= 1");
+    if ((int64_t)M * w->x_n * w->x_n > ((int64_t)1 << 27))
+        return wfail(w, QC_EINVAL, std::string(who) + ": M x_n^2 must be <= 2^27");
+    Dev g(w->device);
+    // (the table of the handle, its lag-0 row (1/2, 0) included; the scale fl(2 / pi) has no h: rho carries it)
+    const hipError_t e = qcart::phase::launch_wigner(w->d_T, w->x_n, w->P, w->ldP, rho, M, out, w->stream);
+    return e == hipSuccess ? QC_OK : qcart::host::hip_fail(w->err, e, who);
 }
 
 int qc_wigner_chunk(int32_t x_n) { return x_n <= 512 ? 2 : 1; }

@@ -48,6 +48,8 @@ class SpatialView(L.DeviceHandle):
             L.check_spatial(L.lib().qc_spatial_create(self.n_levels, ctypes.c_void_p(xs.ctypes.data), self.x_n,
                                                       self.device.index, ctypes.byref(h)))
         self._h = h
+        self._xs = xs
+        self._spacing = None                         # of a uniform x, found on the first density_matrix_of
         self.x = torch.from_numpy(xs).to(self.device)
 
     @classmethod
@@ -147,6 +149,47 @@ class SpatialView(L.DeviceHandle):
                                                 vp(m8.data_ptr()) if m8 is not None else None, t,
                                                 vp(out.data_ptr()), vp(count.data_ptr())))
         return out, count
+
+    def _density_matrices(self, rho):
+        """rho [M, n, n] complex128 contiguous, and whether one matrix was given."""
+        if not isinstance(rho, torch.Tensor):
+            raise ValueError("rho must be a torch tensor")
+        if rho.dtype != torch.complex128:
+            raise ValueError(f"rho must be complex128, not {rho.dtype}")
+        if rho.device != self.device:
+            raise ValueError(f"rho must live on {self.device}, not {rho.device}")
+        one = rho.dim() == 2
+        if one:
+            rho = rho[None]
+        if rho.dim() != 3 or rho.shape[0] < 1 or rho.shape[1] != rho.shape[2]:
+            raise ValueError("rho must be [M, n, n] (or one [n, n] density matrix)")
+        n = int(rho.shape[1])
+        if not 1 <= n <= self.n_levels:
+            raise ValueError(f"n_state must be in [1, {self.n_levels}], not {n}")
+        if int(rho.shape[0]) * self.x_n * self.x_n > 1 << 27:
+            raise ValueError(f"M x_n^2 must be <= 2^27 (M = {int(rho.shape[0])}, x_n = {self.x_n})")
+        return rho.contiguous(), one
+
+    def density_matrix_of(self, rho: torch.Tensor) -> torch.Tensor:
+        """sigma [M, X, X] complex128 (one matrix: [X, X]): the Fock-basis density matrices rho [M, n, n], n <=
+        n_levels, in position space, sigma = h E rho E^T with h the spacing of the view's points, which must be
+        uniform (wigner.WignerView.uniform_grid's criterion): EnsembleView's grid normalisation, so
+        torch.diagonal(sigma).real / h is the position density of rho. rho is assumed Hermitian; sigma is exactly
+        Hermitian with a +0.0 imaginary diagonal (include/qcart.h). Fock views only. Asynchronous."""
+        if self.grid:
+            raise ValueError("SpatialView.density_matrix_of: a grid view's density matrix lives on the grid already")
+        rho, one = self._density_matrices(rho)
+        if self._spacing is None:
+            from .wigner import WignerView
+            self._spacing = WignerView.uniform_grid(self._xs)[1]
+        M, n = int(rho.shape[0]), int(rho.shape[1])
+        out = torch.empty(M, self.x_n, self.x_n, dtype=torch.complex128, device=self.device)
+        vp = ctypes.c_void_p
+        with torch.cuda.device(self.device):
+            self._bind_stream()
+            self._check(L.lib().qc_spatial_congruence(self._h, vp(rho.data_ptr()), n, M, self._spacing,
+                                                      vp(out.data_ptr())))
+        return out[0] if one else out
 
     def table(self) -> torch.Tensor:
         """E [X, n_levels] float64, E[j, n] = psi_n(x[j]): a copy of the device table."""

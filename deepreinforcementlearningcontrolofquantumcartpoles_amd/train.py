@@ -682,13 +682,16 @@ class Trainer:
                 f.write("{} +- {}\n".format(s["mean"], s["sem"]))
         return s["mean"], s["sem"], s["n"]
 
-    def open_loop(self, me, n_control: int, slot: Optional[int] = None) -> dict:
+    def open_loop(self, me, n_control: int, slot: Optional[int] = None, wigner=None) -> dict:
         """The no-control (fixed-force) curve of this loop: the ensemble density matrix of the env's current states
         (through `me.ensemble`, the master equation's own ensemble.EnsembleView, which `me.close()` closes) evolved
         `n_control` control intervals by the master equation `me` (lindblad.MasterEquation, env.master_equation())
         at one slot (None: the F = 0 slot). Returns per-control-step traces [n_control + 1] (entry 0: the starting
         rho) of 'trace', 'purity', 'x', 'x2', 'h', 'boundary' and, for the Fock families, 'n', as device tensors:
-        nothing is waited on, the env and whatever evaluate() returns are untouched."""
+        nothing is waited on, the env and whatever evaluate() returns are untouched. `wigner` (a wigner.WignerView for
+        the env's physics) adds 'wigner' [n_control + 1, X, P], the Wigner function of rho at every entry
+        (WignerView.wigner_of), and 'negativity' [n_control + 1], its negative volume; the other keys are the same
+        tensors with or without it."""
         from .ensemble import EnsembleView
         if isinstance(n_control, bool) or not isinstance(n_control, int) or n_control < 0:
             raise ValueError("Trainer.open_loop: n_control must be an int >= 0")
@@ -697,7 +700,14 @@ class Trainer:
         names = ("x", "x2", "h") + (("n",) if env.ph.fock else ())
         out: dict = {k: [] for k in ("trace", "purity", "boundary") + names}
 
+        if wigner is not None:
+            out["wigner"], out["negativity"] = [], []
+
         def record():
+            if wigner is not None:
+                W = wigner.wigner_of(rho)
+                out["wigner"].append(W)
+                out["negativity"].append(wigner.negative_volume(W))
             out["trace"].append(torch.diagonal(rho).real.sum())
             out["purity"].append(EnsembleView.purity(rho))
             out["boundary"].append(me.boundary_weight(rho))
@@ -795,6 +805,10 @@ def main(argv=None):
                          "purity, x, x2, h, boundary; ho / iho also n) of the envs' starting ensemble over "
                          "--open_loop_steps control intervals at zero force, and t")
     ap.add_argument("--open_loop_steps", type=int, default=90, metavar="T")
+    ap.add_argument("--open_loop_wigner", action="store_true",
+                    help="--open_loop_out: also wigner [T + 1, X, P], the Wigner function of the master equation's rho "
+                         "per control interval, negativity [T + 1], its negative volume, and the axes wigner_x, "
+                         "wigner_p (the key x there is <x>)")
     ap.add_argument("--control_strategy", choices=("DQN", "LQG", "damping", "semiclassical"), default="DQN",
                     help="other than DQN: one evaluation of the analytic baseline controller (ho / iho take LQG only, "
                          "the drivers' --LQG)")
@@ -802,6 +816,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.system in ("ho", "iho") and args.control_strategy not in ("DQN", "LQG"):
         ap.error(f"--control_strategy {args.control_strategy}: the Fock systems take only DQN or LQG")
+    if args.open_loop_wigner and not args.open_loop_out:
+        ap.error("--open_loop_wigner adds to the file of --open_loop_out, which is not given")
     if args.levels_out and args.system in ("iho", "iqo"):
         ap.error(f"--levels_out: --system {args.system} has no bound levels (H is not bounded below)")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -879,10 +895,17 @@ def main(argv=None):
         if args.open_loop_out:
             # before the evaluation moves the envs; it reads their states only
             me = env.master_equation()
-            curve = trainer.open_loop(me, args.open_loop_steps)
+            olview, axes = None, {}
+            if args.open_loop_wigner:
+                from .wigner import WignerView
+                olview = WignerView.for_physics(ph)
+                axes = dict(wigner_x=olview.x.cpu().numpy(), wigner_p=olview.p.cpu().numpy())
+            curve = trainer.open_loop(me, args.open_loop_steps, wigner=olview)
             np.savez(args.open_loop_out, t=np.arange(args.open_loop_steps + 1) * (env.ci * ph.dt),
-                     **{k: v.cpu().numpy() for k, v in curve.items()})
+                     **{k: v.cpu().numpy() for k, v in curve.items()}, **axes)
             me.close()
+            if olview is not None:
+                olview.close()
 
         def write_traces():
             if view is not None:

@@ -55,6 +55,8 @@ class WignerView(L.DeviceHandle):
             L.check_wigner(L.lib().qc_wigner_create(self.x_n, h, ctypes.c_void_p(ps.ctypes.data), self.p_n,
                                                     self.device.index, ctypes.byref(hd)))
         self._h = hd
+        self._ps = ps
+        self._dp = None                              # the spacing of uniform momenta, found by negative_volume
         self.spatial = None
         try:
             if self.n_levels > 0:
@@ -132,6 +134,54 @@ class WignerView(L.DeviceHandle):
             self._bind_stream()
             self._check(L.lib().qc_wigner_eval(self._h, vp(phi.data_ptr()), B, vp(out.data_ptr())))
         return out[0] if one else out
+
+    def wigner_of(self, rho: torch.Tensor) -> torch.Tensor:
+        """W [M, X, P] float64 (one matrix: [X, P]) of density matrices. A grid view takes rho [M, x_n, x_n] complex128
+        with EnsembleView's / MasterEquation's grid normalisation (sum_i rho_ii = 1: a pure state is h phi phi^†); a
+        view with n_levels > 0 takes Fock-basis rho [M, n, n], n <= n_levels, and brings it to the grid through its
+        SpatialView's `density_matrix_of` first. rho is assumed Hermitian: only its lower triangle is read and the
+        imaginary part of the diagonal is ignored (include/qcart.h). W[m] does not depend on the batch.
+        Asynchronous."""
+        if self.spatial is not None:
+            one = isinstance(rho, torch.Tensor) and rho.dim() == 2
+            sigma = self.spatial.density_matrix_of(rho)      # (its refusals: dtype, device, shape, n)
+            sigma = sigma[None] if one else sigma
+        else:
+            if not isinstance(rho, torch.Tensor):
+                raise ValueError("rho must be a torch tensor")
+            if rho.dtype != torch.complex128:
+                raise ValueError(f"rho must be complex128, not {rho.dtype}")
+            if rho.device != self.device:
+                raise ValueError(f"rho must live on {self.device}, not {rho.device}")
+            one = rho.dim() == 2
+            sigma = rho[None] if one else rho
+            if sigma.dim() != 3 or sigma.shape[0] < 1 or sigma.shape[1] != sigma.shape[2]:
+                raise ValueError("rho must be [M, x_n, x_n] (or one [x_n, x_n] density matrix)")
+            if int(sigma.shape[1]) != self.x_n:
+                raise ValueError(f"a grid view takes density matrices of {self.x_n} points, not {int(sigma.shape[1])}")
+            if int(sigma.shape[0]) * self.x_n * self.x_n > 1 << 27:
+                raise ValueError(f"M x_n^2 must be <= 2^27 (M = {int(sigma.shape[0])}, x_n = {self.x_n})")
+            sigma = sigma.contiguous()
+        M = int(sigma.shape[0])
+        out = torch.empty(M, self.x_n, self.p_n, dtype=torch.float64, device=self.device)
+        vp = ctypes.c_void_p
+        with torch.cuda.device(self.device):
+            self._bind_stream()
+            self._check(L.lib().qc_wigner_eval_rho(self._h, vp(sigma.data_ptr()), M, vp(out.data_ptr())))
+        return out[0] if one else out
+
+    def negative_volume(self, W: torch.Tensor) -> torch.Tensor:
+        """sum max(-W, 0) h dp over the last two dimensions of W [..., X, P]: the negative volume of a Wigner function,
+        zero for a Gaussian state. dp is the spacing of `p`, which must be uniform by `uniform_grid`'s criterion (one
+        momentum: dp = 1); ValueError otherwise. Pure torch, nothing is waited on."""
+        if self._dp is None:
+            try:
+                self._dp = self.uniform_grid(self._ps)[1]
+            except ValueError as e:
+                raise ValueError(f"negative_volume needs uniform momenta: p as {e}") from None
+        if not isinstance(W, torch.Tensor) or W.dim() < 2 or tuple(W.shape[-2:]) != (self.x_n, self.p_n):
+            raise ValueError(f"W must be [..., {self.x_n}, {self.p_n}]")
+        return torch.clamp(-W, min=0.).sum(dim=(-2, -1)) * (self.h * self._dp)
 
     def mean_wigner(self, psi: torch.Tensor, mask: Optional[torch.Tensor] = None):
         """(mean [X, P] float64, count int64 scalar tensor): the mean of `wigner` over the envs whose mask is set (bool

@@ -880,6 +880,28 @@ int qc_spatial_probability(qc_spatial* s, const void* psi, int32_t B, int32_t n_
 /* mask: device uint8 [B] or NULL; out: device [x_n]; count: device, may be NULL */
 int qc_spatial_mean(qc_spatial* s, const void* psi, int32_t B, int32_t n_state, const uint8_t* mask, double threshold,
                     double* out, int64_t* count);
+/* The change of basis of density matrices, Fock -> position: sigma_m = scale * E rho_m E^T,
+ *   sigma[i][j] = scale * sum_{m, n < n_state} E[i][m] rho[m][n] E[j][n],
+ * rho [M][n_state][n_state] complex128 and sigma [M][x_n][x_n] complex128 on the device (they must not overlap), E the
+ * handle's table, which is real. With scale = h, the spacing of a uniform x, sigma has qc_ensemble's grid normalisation
+ * (Tr sigma = 1 for Tr rho = 1 when the grid holds the states) and Re sigma[i][i] / h is the position density. The
+ * input is ASSUMED Hermitian and is not checked: all of rho is read as it stands, and the output is the exactly
+ * Hermitian matrix whose lower triangle is that of the product: sigma[i][j] for j <= i and sigma[j][i] are written from
+ * the same values (the sign bit of the imaginary part flipped), the diagonal's imaginary part is +0.0. Two kernels on
+ * v_mfma_f64_16x16x4_f64 in the manner of qc_lindblad_congruence, Zt = (E rho)^T (all of it), then the elements of
+ * Zt^T E^T on or below the diagonal. The order of every sum is a function of n_state alone: the contraction index k
+ * runs in ascending groups of four from accumulators that start at +0, one matrix instruction per group and
+ * accumulator (rows and k past the matrix enter as exact zeros selected by address; what memory holds there is never
+ * multiplied):
+ *   Zt[r][c]:  re += Re rho[k][r] * E[c][k];  im += Im rho[k][r] * E[c][k];
+ *   acc[i][j]: re += Re Zt[k][i] * E[j][k];   im += Im Zt[k][i] * E[j][k];
+ * then sigma[i][j] = (fl(scale * re), fl(scale * im)). Element (m, i, j) does not depend on M, on where rho_m sits in
+ * the batch or on the other matrices of the call (a launch of fewer than 2048 blocks of 32 x 32 elements runs one
+ * 16 x 16 tile per workgroup instead of 2 x 2: the same instructions in the same order). No atomics. Zt lives in a
+ * buffer of the handle that grows with M (the only allocation the call may make). Refused with a text, before anything
+ * is launched: a grid view, n_state outside [1, n_levels], M < 1, null pointers, a scale that is not finite,
+ * M x_n^2 > 2^27. */
+int qc_spatial_congruence(qc_spatial* s, const void* rho, int32_t n_state, int32_t M, double scale, void* sigma);
 
 /* ---- phase-space view: the Wigner function of a batch of wavefunctions on the device --------------------------------
  * For a wavefunction phi sampled on a uniform grid (phi_i = phi(x_0 + i h), sum_i h |phi_i|^2 = 1) and momenta p[P]:
@@ -916,6 +938,19 @@ int qc_wigner_mean(qc_wigner* w, const void* phi, int32_t B, const uint8_t* mask
 /* the mean's order (above): envs per chunk, and the number of splits (0 for arguments out of range) */
 int qc_wigner_chunk(int32_t x_n);
 int qc_wigner_splits(int32_t B, int32_t x_n, int32_t P);
+/* The Wigner function of density matrices on the grid. rho [M][x_n][x_n] complex128 on the device, normalised as
+ * qc_ensemble normalises a grid family's (sum_i rho[i][i] = 1: a pure state is rho = h phi phi^†). With
+ * L_ik = rho[i + k][i - k], an element of the LOWER triangle,
+ *   W[i][j] = (1 / pi) ( Re rho[i][i] + 2 sum_{k = 1 .. K_i} ( Re L_ik cos(2 p_j k h) + Im L_ik sin(2 p_j k h) ) ),
+ * which is the W above with conj(phi_{i+k}) phi_{i-k} = rho[i-k][i+k] / h read through Hermiticity. The input is
+ * ASSUMED Hermitian and is not checked: only the elements with row >= col and an even row - col are read, and the
+ * imaginary part of the diagonal is ignored (what the rest of memory holds, NaN included, does not matter). out is
+ * W [M][x_n][P] (64-bit offsets). An element is fl(s * acc), s = fl(2 / pi), acc the fp64 matrix pipe's sum, from +0,
+ * over the lags in ascending steps of four, per step first (Re L, cos) and then (Im L, sin), lag 0 entering as
+ * (Re rho[i][i], 1/2) and (+0, 0); lags past K_i enter as exact zeros selected by address. Element (m, i, j) depends
+ * on rho_m alone: not on M, nor on where matrix m sits. It uses the handle's table and allocates nothing. M < 1, null
+ * pointers and M x_n^2 > 2^27 are refused with a text before anything is launched. Asynchronous. */
+int qc_wigner_eval_rho(qc_wigner* w, const void* rho, int32_t M, double* out);
 
 /* ---- ensemble view: the density matrix of a batch of states on the device -------------------------------------------
  * For states psi [B][N] complex128 (contiguous, on the device), N in [1, 2048]:
