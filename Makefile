@@ -8,8 +8,8 @@ LIB := $(PKG)/libqcart.so
 # arithmetic; an env's trajectory never depends on which workgroup shape it ran in (the backend's "fast"
 # contraction fused differently per instantiation)
 HIPFLAGS ?= -O3 -std=c++17 --offload-arch=gfx950 -fPIC -Wall -Wno-unused-function -ffp-contract=on
-OBJS := $(addprefix $(CSRC)/build/,qcart_k_ho.o qcart_k_iho.o qcart_k_grid.o qcart_k_f32.o qcart_k_group.o qcart_record.o qcart_noise.o qcart_replay.o qcart_actor.o qcart_learner.o qcart_mlearner.o qcart_dispatch.o qcart_api.o qcart_tables.o qcart_server.o qcart_env.o qcart_sched.o qcart_monitor.o qcart_spatial.o qcart_wigner.o qcart_ensemble.o qcart_levels.o qcart_lindblad.o qcart_phase.o)
-HDRS := include/qcart.h $(CSRC)/qcart_mt.hpp $(CSRC)/qcart_expt.hpp $(CSRC)/qcart_kargs.hpp $(CSRC)/qcart_tables.hpp $(CSRC)/qcart_kernels.hpp $(CSRC)/qcart_mfma.hpp $(CSRC)/qcart_dqn.hpp $(CSRC)/qcart_host.hpp $(CSRC)/qcart_learner.hpp $(CSRC)/qcart_state.hpp $(CSRC)/qcart_sched.hpp $(CSRC)/qcart_monitor.hpp $(CSRC)/qcart_spatial.hpp $(CSRC)/qcart_wigner.hpp $(CSRC)/qcart_ensemble.hpp $(CSRC)/qcart_levels.hpp $(CSRC)/qcart_lindblad.hpp $(CSRC)/qcart_phase.hpp $(CSRC)/qcart_wigner_tiles.hpp $(CSRC)/qcart_shm.h
+OBJS := $(addprefix $(CSRC)/build/,qcart_k_ho.o qcart_k_iho.o qcart_k_grid.o qcart_k_f32.o qcart_k_group.o qcart_record.o qcart_noise.o qcart_replay.o qcart_actor.o qcart_learner.o qcart_mlearner.o qcart_dispatch.o qcart_api.o qcart_tables.o qcart_server.o qcart_env.o qcart_sched.o qcart_monitor.o qcart_spatial.o qcart_wigner.o qcart_ensemble.o qcart_levels.o qcart_lindblad.o qcart_phase.o qcart_filter.o)
+HDRS := include/qcart.h $(CSRC)/qcart_mt.hpp $(CSRC)/qcart_expt.hpp $(CSRC)/qcart_kargs.hpp $(CSRC)/qcart_tables.hpp $(CSRC)/qcart_kernels.hpp $(CSRC)/qcart_mfma.hpp $(CSRC)/qcart_dqn.hpp $(CSRC)/qcart_host.hpp $(CSRC)/qcart_learner.hpp $(CSRC)/qcart_state.hpp $(CSRC)/qcart_sched.hpp $(CSRC)/qcart_monitor.hpp $(CSRC)/qcart_spatial.hpp $(CSRC)/qcart_wigner.hpp $(CSRC)/qcart_ensemble.hpp $(CSRC)/qcart_levels.hpp $(CSRC)/qcart_lindblad.hpp $(CSRC)/qcart_phase.hpp $(CSRC)/qcart_filter.hpp $(CSRC)/qcart_wigner_tiles.hpp $(CSRC)/qcart_shm.h
 # the step server's client side: plain C (POSIX shared memory + futexes), no HIP
 CLIENT := $(PKG)/libqcart_client.so
 

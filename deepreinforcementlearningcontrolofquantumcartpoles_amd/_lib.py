@@ -63,7 +63,8 @@ EXPORTS = (
     "qc_levels_amplitudes", "qc_levels_populations", "qc_levels_mean",
     "qc_lindblad_tables", "qc_lindblad_create", "qc_lindblad_destroy", "qc_lindblad_last_error",
     "qc_lindblad_set_stream", "qc_lindblad_dim", "qc_lindblad_evolve", "qc_lindblad_congruence",
-    "qc_lindblad_take_errors",
+    "qc_lindblad_take_errors", "qc_lindblad_set_efficiency", "qc_lindblad_efficiency",
+    "qc_lindblad_evolve_conditional", "qc_lindblad_filter_draws", "qc_lindblad_efficiency_table", "qc_lindblad_xi",
 ) + tuple(f"qc_{kind}_state_{op}" for kind in ("actor", "mactor", "replay", "learner", "mlearner", "sched", "monitor")
           for op in ("bytes", "export", "import"))   # checkpoint: a handle's whole state as one host buffer
 
@@ -562,6 +563,12 @@ def lib() -> ctypes.CDLL:
     L.qc_lindblad_evolve.argtypes = [vp, vp, i32, vp, i32, i32]
     L.qc_lindblad_congruence.argtypes = [vp, vp, vp, vp, vp, i32]
     L.qc_lindblad_take_errors.argtypes = [vp]
+    L.qc_lindblad_set_efficiency.argtypes = [vp, d]
+    L.qc_lindblad_efficiency.argtypes = [vp, P(d)]
+    L.qc_lindblad_evolve_conditional.argtypes = [vp, vp, i32, vp, i32, i32, u64, vp, i64, vp, vp, vp]
+    L.qc_lindblad_filter_draws.argtypes = [u64, ctypes.c_uint32, u64, P(d), P(d)]
+    L.qc_lindblad_xi.argtypes = [vp, vp]
+    L.qc_lindblad_efficiency_table.argtypes = [P(QcParams), d, d, d, vp]
     L.qc_mlearner_stats.argtypes = [vp, P(QcLearnerStats)]
     L.qc_mlearner_grads.argtypes = [vp, P(QcDqnLayer)]
     L.qc_mlearner_apply.argtypes = [vp, P(QcDqnLayer)]

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/qcart.h"
+#include "qcart_filter.hpp"
 #include "qcart_host.hpp"
 #include "qcart_lindblad.hpp"
 #include "qcart_tables.hpp"
@@ -222,7 +223,18 @@ struct qc_lindblad {
     double2* d_Z = nullptr;      // [z_cap][N][N], of the largest M seen
     size_t z_cap = 0;
     double2* d_zero = nullptr;   // one complex zero: the operand of what does not enter
-    int32_t* d_flag = nullptr;   // raised by a slot outside [0, J)
+    int32_t* d_flag = nullptr;   // [3]: [0] raised by a slot outside [0, J), [1] by a matrix the conditional evolution
+                                 // could not step, [2] where its congruences' own slot word goes (never read)
+    // the conditional evolution (qc_lindblad_set_efficiency, qc_lindblad_evolve_conditional)
+    double dt = 0., gamma = 0., eta = -1.;
+    double a = 0., s = 0.;       // eta gamma dt / 2 and 1 / sqrt(4 a)
+    std::vector<ld> xi;          // X's eigenvalues in long double
+    double* d_xi = nullptr;      // [N]
+    double* d_ge = nullptr;      // G^(1 - eta) [N][N] (not read at eta = 1)
+    double2* d_backup = nullptr; // [m_cap][N][N]: rho as a call found it
+    double* d_v = nullptr;       // [m_cap][N]
+    int32_t* d_eff = nullptr;    // [m_cap] the slots the call's congruences read, then [m_cap] status words
+    size_t m_cap = 0;
 };
 
 namespace {
@@ -274,9 +286,30 @@ int grow_z(qc_lindblad* h, int32_t M, const char* who) {
     return QC_OK;
 }
 
-// y = g o (A x A^†) for the transposed operands at (stride 0: one for every slot)
+// the conditional evolution's per-matrix buffers, of the largest M seen
+int grow_m(qc_lindblad* h, int32_t M, const char* who) {
+    if ((size_t)M <= h->m_cap) return QC_OK;
+    void* old[] = {h->d_backup, h->d_v, h->d_eff};
+    for (void* p : old)
+        if (p) (void)hipFree(p);                       // (waits for the device)
+    h->d_backup = nullptr;
+    h->d_v = nullptr;
+    h->d_eff = nullptr;
+    h->m_cap = 0;
+    const size_t N = (size_t)h->N;
+    hipError_t e = hipMalloc((void**)&h->d_backup, (size_t)M * N * N * sizeof(double2));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_v, (size_t)M * N * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_eff, (size_t)M * 2 * sizeof(int32_t));
+    if (e != hipSuccess) return qcart::host::hip_fail(h->err, e, who);
+    h->m_cap = (size_t)M;
+    return QC_OK;
+}
+
+// y = g o (A x A^†) for the transposed operands at (stride 0: one for every slot); flag: the word a slot outside
+// [0, J) raises (null: the handle's)
 int congruence(qc_lindblad* h, const double2* at, size_t at_stride, const double* g, const double2* x, double2* y,
-               int32_t M, const int32_t* slots, int32_t default_slot, int32_t J, const char* who) {
+               int32_t M, const int32_t* slots, int32_t default_slot, int32_t J, const char* who,
+               int32_t* flag = nullptr) {
     Args a{};
     a.at = at;
     a.at_stride = at_stride;
@@ -284,7 +317,7 @@ int congruence(qc_lindblad* h, const double2* at, size_t at_stride, const double
     a.default_slot = default_slot;
     a.J = J;
     a.zero = h->d_zero;
-    a.flag = h->d_flag;
+    a.flag = flag ? flag : h->d_flag;
     a.N = h->N;
     // the block shape changes which workgroup computes an element, never the element: its sums run in the same order
     const int rb32 = (h->N + 31) / 32;
@@ -370,6 +403,11 @@ int qc_lindblad_create(const qc_params* p, double dt, double gamma, const double
     h->J = J;
     h->fock = src.fock;
     h->device = device;
+    h->dt = dt;
+    h->gamma = gamma;
+    h->xi = basis_.xi;
+    std::vector<double> xi64((size_t)N);
+    for (int32_t i = 0; i < N; ++i) xi64[(size_t)i] = (double)basis_.xi[(size_t)i];
     Dev g(device);
     const size_t cbytes = plane * sizeof(double2), rbytes = plane * sizeof(double);
     hipError_t e = hipMalloc((void**)&h->d_T, (size_t)J * cbytes);
@@ -381,8 +419,10 @@ int qc_lindblad_create(const qc_params* p, double dt, double gamma, const double
     if (e == hipSuccess) e = hipMalloc((void**)&h->d_A, cbytes);
     if (e == hipSuccess) e = hipMalloc((void**)&h->d_zero, sizeof(double2));
     if (e == hipSuccess) e = hipMemset(h->d_zero, 0, sizeof(double2));
-    if (e == hipSuccess) e = hipMalloc((void**)&h->d_flag, sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemset(h->d_flag, 0, sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_flag, 3 * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemset(h->d_flag, 0, 3 * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->d_xi, (size_t)N * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpy(h->d_xi, xi64.data(), (size_t)N * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess && h->fock) {
         // the real W, staged in d_A's memory, widened to the two complex operands of the basis changes
         e = hipMalloc((void**)&h->d_W, cbytes);
@@ -412,7 +452,8 @@ void qc_lindblad_destroy(qc_lindblad* h) {
     {
         Dev g(h->device);
         (void)hipDeviceSynchronize();
-        void* all[] = {h->d_T, h->d_gh, h->d_gf, h->d_W, h->d_Wt, h->d_A, h->d_Z, h->d_zero, h->d_flag};
+        void* all[] = {h->d_T,    h->d_gh,   h->d_gf, h->d_W,  h->d_Wt,     h->d_A, h->d_Z,
+                       h->d_zero, h->d_flag, h->d_xi, h->d_ge, h->d_backup, h->d_v, h->d_eff};
         for (void* p : all)
             if (p) (void)hipFree(p);
     }
@@ -471,13 +512,130 @@ int qc_lindblad_congruence(qc_lindblad* h, const void* A, const double* g, const
 int qc_lindblad_take_errors(qc_lindblad* h) {
     if (!h) return QC_EINVAL;
     Dev g(h->device);
-    int32_t flag = 0;
+    int32_t flag[2] = {0, 0};
     hipError_t e = hipStreamSynchronize(h->stream);
-    if (e == hipSuccess) e = hipMemcpy(&flag, h->d_flag, sizeof(flag), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && flag) e = hipMemset(h->d_flag, 0, sizeof(flag));
+    if (e == hipSuccess) e = hipMemcpy(flag, h->d_flag, sizeof(flag), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && (flag[0] || flag[1])) e = hipMemset(h->d_flag, 0, sizeof(flag));
     if (e != hipSuccess) return qcart::host::hip_fail(h->err, e, "qc_lindblad_take_errors");
-    if (!flag) return QC_OK;
-    return lfail(h, QC_EINVAL, "a slot out of [0, J) reached qc_lindblad_evolve (that rho was left untouched)");
+    if (!flag[0] && !flag[1]) return QC_OK;
+    const char* slot = "a slot out of [0, J) reached qc_lindblad_evolve (that rho was left untouched)";
+    const char* dead = "a rho could not be stepped by qc_lindblad_evolve_conditional: its diagonal's sum, the outcome "
+                       "or the outcome's weight Z was not finite and > 0 (that rho was left untouched)";
+    return lfail(h, QC_EINVAL, flag[0] && flag[1] ? std::string(slot) + "; " + dead : flag[0] ? slot : dead);
+}
+
+int qc_lindblad_set_efficiency(qc_lindblad* h, double eta) {
+    if (!h) return QC_EINVAL;
+    if (const char* bad = qcart::filter::bad_efficiency(eta, h->gamma))
+        return lfail(h, QC_EINVAL, std::string("qc_lindblad_set_efficiency: ") + bad);
+    const char* who = "qc_lindblad_set_efficiency";
+    const size_t plane = (size_t)h->N * (size_t)h->N;
+    Dev g(h->device);
+    if (eta < 1.) {
+        // G^(1 - eta): the dephasing the record does not account for, gamma (1 - eta) formed in long double
+        std::vector<double> ge(plane);
+        qcart::filter::efficiency_table(h->N, h->xi.data(), h->dt, h->gamma, eta, ge.data());
+        hipError_t e = hipStreamSynchronize(h->stream);                  // (no launch still reads the old table)
+        if (e == hipSuccess && !h->d_ge) e = hipMalloc((void**)&h->d_ge, plane * sizeof(double));
+        if (e == hipSuccess) e = hipMemcpy(h->d_ge, ge.data(), plane * sizeof(double), hipMemcpyHostToDevice);
+        if (e != hipSuccess) return qcart::host::hip_fail(h->err, e, who);
+    }
+    h->eta = eta;
+    qcart::filter::constants(eta, h->gamma, h->dt, &h->a, &h->s);
+    return QC_OK;
+}
+
+int qc_lindblad_efficiency(const qc_lindblad* h, double* eta) {
+    if (!h || !eta) return QC_EINVAL;
+    *eta = h->eta;
+    return QC_OK;
+}
+
+int qc_lindblad_xi(qc_lindblad* h, double* xi) {
+    if (!h) return QC_EINVAL;
+    if (!xi) return lfail(h, QC_EINVAL, "qc_lindblad_xi: xi is required");
+    Dev g(h->device);
+    const hipError_t e = hipMemcpyAsync(xi, h->d_xi, (size_t)h->N * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
+    return e == hipSuccess ? QC_OK : qcart::host::hip_fail(h->err, e, "qc_lindblad_xi");
+}
+
+int qc_lindblad_efficiency_table(const qc_params* p, double dt, double gamma, double eta, double* g) {
+    const char* who = "qc_lindblad_efficiency_table: ";
+    if (!p || !g) return g_lindblad_err.fail(std::string(who) + "params and g are required", QC_EINVAL);
+    const char* bad = bad_step(dt, gamma);
+    if (!bad) bad = qcart::filter::bad_efficiency(eta, gamma);
+    if (bad) return g_lindblad_err.fail(std::string(who) + bad, QC_EINVAL);
+    qcart::OpHost op;
+    Source s;
+    std::string err;
+    if (const int rc = make_source(p, op, s, err)) return g_lindblad_err.fail(who + err, rc);
+    Basis b;
+    const char* why = nullptr;
+    if (const int rc = make_basis(s, b, &why)) return g_lindblad_err.fail(std::string(who) + (why ? why : "failed"), rc);
+    qcart::filter::efficiency_table(s.N, b.xi.data(), dt, gamma, eta, g);
+    return QC_OK;
+}
+
+int qc_lindblad_filter_draws(uint64_t seed, uint32_t stream, uint64_t step, double* u, double* z) {
+    if (!u || !z) return QC_EINVAL;
+    qcart::filter::draws(seed, stream, step, u, z);
+    return QC_OK;
+}
+
+int qc_lindblad_evolve_conditional(qc_lindblad* h, void* rho, int32_t M, const int32_t* slots, int32_t default_slot,
+                                   int32_t n_steps, uint64_t seed, const int32_t* streams, int64_t first_step,
+                                   const double* draws, const double* record_in, double* record_out) {
+    if (!h) return QC_EINVAL;
+    if (const char* bad = qcart::filter::bad_conditional(rho, M, h->N, slots, default_slot, h->J, n_steps, h->eta,
+                                                         first_step, draws, record_in))
+        return lfail(h, QC_EINVAL, std::string("qc_lindblad_evolve_conditional: ") + bad);
+    if (n_steps == 0) return QC_OK;
+    const char* who = "qc_lindblad_evolve_conditional";
+    Dev g(h->device);
+    if (const int rc = grow_z(h, M, who)) return rc;
+    if (const int rc = grow_m(h, M, who)) return rc;
+    double2* r = (double2*)rho;
+    const size_t plane = (size_t)h->N * (size_t)h->N;
+    qcart::filter::Call c{};
+    c.sigma = rho;
+    c.xi = h->d_xi;
+    c.N = h->N;
+    c.M = M;
+    c.J = h->J;
+    c.slots = slots;
+    c.default_slot = default_slot;
+    c.eff = h->d_eff;
+    c.status = h->d_eff + M;
+    c.flags = h->d_flag;
+    c.v = h->d_v;
+    c.a = h->a;
+    c.s = h->s;
+    c.seed = seed;
+    c.streams = streams;
+    c.stream = h->stream;
+    auto hip = [&](hipError_t e) { return e == hipSuccess ? QC_OK : qcart::host::hip_fail(h->err, e, who); };
+    if (const int rc = hip(hipMemcpyAsync(h->d_backup, rho, (size_t)M * plane * sizeof(double2),
+                                          hipMemcpyDeviceToDevice, h->stream)))
+        return rc;
+    if (const int rc = hip(qcart::filter::launch_begin(c))) return rc;
+    // the congruences read the call's own slots (eff: -1 from the moment a matrix is dead) and raise a word nobody reads
+    int32_t* quiet = h->d_flag + 2;
+    if (h->fock)
+        if (const int rc = congruence(h, h->d_W, 0, nullptr, r, r, M, c.eff, 0, h->J, who, quiet)) return rc;
+    const double* ge = h->eta < 1. ? h->d_ge : nullptr;
+    for (int32_t n = 0; n < n_steps; ++n) {
+        if (const int rc = congruence(h, h->d_T, plane, ge, r, r, M, c.eff, 0, h->J, who, quiet)) return rc;
+        const size_t at = (size_t)n * (size_t)M;
+        if (const int rc = hip(qcart::filter::launch_draw(c, (uint64_t)first_step + (uint64_t)n,
+                                                          draws ? draws + 2 * at : nullptr,
+                                                          record_in ? record_in + at : nullptr,
+                                                          record_out ? record_out + at : nullptr)))
+            return rc;
+        if (const int rc = hip(qcart::filter::launch_apply(c))) return rc;
+    }
+    if (h->fock)
+        if (const int rc = congruence(h, h->d_Wt, 0, nullptr, r, r, M, c.eff, 0, h->J, who, quiet)) return rc;
+    return hip(qcart::filter::launch_restore(c, h->d_backup));
 }
 
 }  // extern "C"

@@ -280,8 +280,9 @@ inline int propagator(const Source& s, double dt, double force, const double* W,
 }
 
 // G½ and G [N][N] from the long double xi (either may be null)
-inline void gauss(int32_t N, const ld* xi, double dt, double gamma, double* g_half, double* g_full) {
-    const ld gd = (ld)gamma * (ld)dt;
+// (dt and gamma in long double: a double converts exactly; the conditional evolution passes gamma (1 - eta) unrounded)
+inline void gauss(int32_t N, const ld* xi, ld dt, ld gamma, double* g_half, double* g_full) {
+    const ld gd = gamma * dt;
     for (int i = 0; i < N; ++i)
         for (int j = 0; j <= i; ++j) {
             const ld d = xi[i] - xi[j], a = gd * d * d;

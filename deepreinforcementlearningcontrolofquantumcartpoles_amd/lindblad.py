@@ -132,6 +132,16 @@ class MasterEquation(L.DeviceHandle):
         M = 1 if rho.dim() == 2 else int(rho.shape[0])
         if isinstance(n_steps, bool) or not isinstance(n_steps, int) or n_steps < 0:
             raise ValueError("n_steps must be an int >= 0")
+        sp, default = self._slots(slots, M)
+        vp = ctypes.c_void_p
+        with torch.cuda.device(self.device):
+            self._bind_stream()
+            self._check(L.lib().qc_lindblad_evolve(self._h, vp(rho.data_ptr()), M,
+                                                   vp(sp.data_ptr()) if sp is not None else None, default, n_steps))
+        return rho
+
+    def _slots(self, slots, M: int):
+        """(the device int32 [M] tensor or None, the slot for all) of `evolve`'s slots argument."""
         sp, default = None, 0
         if slots is None:
             if self.zero_force_slot is None:
@@ -149,12 +159,7 @@ class MasterEquation(L.DeviceHandle):
             default = slots
         else:
             raise ValueError(f"slots must be an int or an int32 [{M}] tensor")
-        vp = ctypes.c_void_p
-        with torch.cuda.device(self.device):
-            self._bind_stream()
-            self._check(L.lib().qc_lindblad_evolve(self._h, vp(rho.data_ptr()), M,
-                                                   vp(sp.data_ptr()) if sp is not None else None, default, n_steps))
-        return rho
+        return sp, default
 
     def congruence(self, A: torch.Tensor, x: torch.Tensor, g: Optional[torch.Tensor] = None,
                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -188,10 +193,125 @@ class MasterEquation(L.DeviceHandle):
         return out
 
     def take_errors(self) -> None:
-        """Raises QCartError if a slot outside [0, J) has reached `evolve` since the last call. Synchronises."""
+        """Raises QCartError if a slot outside [0, J) has reached `evolve` or `evolve_conditional`, or a rho that
+        `evolve_conditional` could not step, since the last call. Synchronises."""
         with torch.cuda.device(self.device):
             self._bind_stream()
             self._check(L.lib().qc_lindblad_take_errors(self._h))
+
+    # ------------------------------------------------------------------ the conditional evolution
+    def set_efficiency(self, eta: float) -> None:
+        """The detection efficiency eta in (0, 1] of `evolve_conditional`: builds the table G^(1 - eta) on the host and
+        uploads it (may synchronise). A refused eta (or a handle whose gamma is 0) raises ValueError."""
+        with torch.cuda.device(self.device):
+            self._bind_stream()
+            rc = L.lib().qc_lindblad_set_efficiency(self._h, float(eta))
+        if rc == -1:
+            raise ValueError(L.lib().qc_lindblad_last_error(self._h).decode())
+        self._check(rc)
+
+    @property
+    def eta(self) -> Optional[float]:
+        """The detection efficiency, None while unset."""
+        e = ctypes.c_double(-1.0)
+        self._check(L.lib().qc_lindblad_efficiency(self._h, ctypes.byref(e)))
+        return None if e.value < 0 else e.value
+
+    @property
+    def xi(self) -> torch.Tensor:
+        """X's eigenvalues, float64 [N] on the device: the measurement basis of `evolve` and `evolve_conditional`
+        (ascending for the Fock families, the grid points otherwise): a copy of the handle's own, made once.
+        Asynchronous."""
+        if "xi" not in self._ops:
+            xi = torch.empty(self.n, dtype=torch.float64, device=self.device)
+            with torch.cuda.device(self.device):
+                self._bind_stream()
+                self._check(L.lib().qc_lindblad_xi(self._h, ctypes.c_void_p(xi.data_ptr())))
+            self._ops["xi"] = xi
+        return self._ops["xi"]
+
+    def _per_step(self, t, what: str, n_steps: int, M: int, last: tuple = ()) -> torch.Tensor:
+        shape = (n_steps, M) + last
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) != shape:
+            raise ValueError(f"{what} must be a float64 {list(shape)} tensor")
+        if t.device != self.device:
+            raise ValueError(f"{what} must live on {self.device}, not {t.device}")
+        if not t.is_contiguous():
+            raise ValueError(f"{what} must be contiguous")
+        return t
+
+    def evolve_conditional(self, rho: torch.Tensor, n_steps: int, slots=None, *, seed: int = 0, streams=None,
+                           first_step: int = 0, draws=None, record=None, want_record: bool = False):
+        """rho after n_steps steps of the conditional master equation at the efficiency of `set_efficiency`, in place:
+        rho along one measurement record per matrix (include/qcart.h). The record is sampled from Philox
+        keyed by `seed` at (first_step + n, streams[m]) (streams: a device int32 [M] tensor, None: m), or from
+        `draws` (float64 [n_steps, M, 2]: u in (0, 1) and a standard normal z), or it is given: `record` (float64
+        [n_steps, M], the outcomes y) makes the call a filter and nothing is drawn; `record` with `draws` is refused.
+        slots as `evolve`'s. Returns rho, or with want_record = True (rho, y [n_steps, M]). A rho that cannot be
+        stepped (a slot out of range, a diagonal that is not finite, a record that contradicts it) is left untouched,
+        its y are NaN from that step on, and `take_errors` reports it. Asynchronous."""
+        rho = self._matrices(rho)
+        M = 1 if rho.dim() == 2 else int(rho.shape[0])
+        if isinstance(n_steps, bool) or not isinstance(n_steps, int) or n_steps < 0:
+            raise ValueError("n_steps must be an int >= 0")
+        if isinstance(first_step, bool) or not isinstance(first_step, int) or first_step < 0:
+            raise ValueError("first_step must be an int >= 0")
+        if isinstance(seed, bool) or not isinstance(seed, int) or not 0 <= seed < 2 ** 64:
+            raise ValueError("seed must be an int in [0, 2^64)")
+        if self.eta is None:
+            raise ValueError("the efficiency is not set (set_efficiency first)")
+        if draws is not None and record is not None:
+            raise ValueError("record and draws exclude each other")
+        sp, default = self._slots(slots, M)
+        if streams is not None:
+            if not isinstance(streams, torch.Tensor) or streams.dtype != torch.int32 or tuple(streams.shape) != (M,):
+                raise ValueError(f"streams must be an int32 [{M}] tensor")
+            if streams.device != self.device:
+                raise ValueError(f"streams must live on {self.device}, not {streams.device}")
+            streams = streams.contiguous()
+        if draws is not None:
+            draws = self._per_step(draws, "draws", n_steps, M, (2,))
+        if record is not None:
+            record = self._per_step(record, "record", n_steps, M)
+        y = torch.empty((n_steps, M), dtype=torch.float64, device=self.device) if want_record else None
+        vp = ctypes.c_void_p
+        ptr = lambda t: vp(t.data_ptr()) if t is not None else None   # noqa: E731
+        with torch.cuda.device(self.device):
+            self._bind_stream()
+            self._check(L.lib().qc_lindblad_evolve_conditional(self._h, vp(rho.data_ptr()), M, ptr(sp), default,
+                                                               n_steps, seed, ptr(streams), first_step, ptr(draws),
+                                                               ptr(record), ptr(y)))
+        return (rho, y) if want_record else rho
+
+    def controller_operator(self, name: str) -> torch.Tensor:
+        """`controller_operator` (this module) of the handle's physics on its device, made once per name."""
+        key = "c:" + name
+        if key not in self._ops:
+            self._ops[key] = torch.from_numpy(controller_operator(self.physics, name)).to(self.device)
+        return self._ops[key]
+
+    @staticmethod
+    def expectations(rho: torch.Tensor, op: torch.Tensor) -> torch.Tensor:
+        """Re Tr(rho_m op) of every matrix of a batch [M, N, N] (EnsembleView.expectation's quantity per matrix): a
+        float64 [M] tensor."""
+        return (rho * op.to(rho.dtype).transpose(0, 1)).sum(dim=(-2, -1)).real
+
+    def analytic_slots(self, rho: torch.Tensor, strategy: str = "LQG", con_parameter: float = 0.0) -> torch.Tensor:
+        """The slots (= actions) of the drivers' analytic baseline controllers on a batch of rho, int32 [M]: the
+        formulas of IHO/main_parallel.py:194-206 (Fock 'LQG') and QO/controllers.py:7-29 with QO/main_parallel.py:165-181
+        (grid 'LQG', 'damping', 'semiclassical'), with Tr(rho O) in the place of <psi|O|psi>, evaluated in float64 torch
+        on the device (`baseline_slots`). It is NOT a reproduction of the Fock branch's float32 network input (the
+        reference, and `BatchedEnv.analytic_actions`, round x and p to float32 first): the two agree wherever the force
+        is not within float32 rounding of a tie between two actions. Valid only for a handle whose forces are the
+        physics' own action grid (slot = action); refused otherwise. Asynchronous."""
+        ph = self.physics
+        if self.forces != tuple(float(ph.force(a)) for a in range(ph.n_actions)):
+            raise ValueError("analytic_slots needs the physics' own action grid as the handle's forces (slot = action)")
+        rho = self._matrices(rho)
+        if rho.dim() == 2:
+            rho = rho[None]
+        return baseline_slots(ph, lambda k: self.expectations(rho, self.controller_operator(k)), strategy,
+                              con_parameter)
 
     # ------------------------------------------------------------------ operators and what rho gives
     def operator(self, name: str) -> torch.Tensor:
@@ -231,3 +351,71 @@ class MasterEquation(L.DeviceHandle):
         if self.physics.fock:
             return d[..., -5:].sum(dim=-1)
         return d[..., :6].sum(dim=-1) + d[..., -6:].sum(dim=-1)
+
+
+def controller_operator(ph: cfg.Physics, name: str) -> np.ndarray:
+    """The dense [N, N] complex128 operators the drivers' baseline controllers take expectation values of, in the
+    states' basis: 'x', 'x2', 'p', 'p2', 'xp' (= x p + p x), 'x3', 'xpx' (= x p x), built from the truncated X and P
+    (Fock: x = sqrt(1/2) (a^† + a), p = i sqrt(1/2) (a^† - a); grid: x the points, p = -i D1, the 8th-order
+    first-difference stencil over the grid spacing)."""
+    if name not in ("x", "x2", "p", "p2", "xp", "x3", "xpx"):
+        raise ValueError(f"no controller operator {name!r} (x, x2, p, p2, xp, x3, xpx)")
+    n = int(ph.dim)
+    if ph.fock:
+        up = np.array([math.sqrt(float(i + 1)) * math.sqrt(0.5) for i in range(n - 1)])
+        X = np.diag(up, 1) + np.diag(up, -1)
+        Pm = 1.0j * (np.diag(up, -1) - np.diag(up, 1))
+    else:
+        X = np.diag(ph.grid_size * (np.arange(n) - (n - 1) // 2).astype(np.float64))
+        d = np.zeros((n, n))
+        for k, c in ((1, 672 / 840), (2, -168 / 840), (3, 32 / 840), (4, -3 / 840)):
+            d += np.diag(np.full(n - k, c), k) - np.diag(np.full(n - k, c), -k)
+        Pm = -1.0j * (d / ph.grid_size)
+    m = {"x": lambda: X, "x2": lambda: X @ X, "p": lambda: Pm, "p2": lambda: Pm @ Pm,
+         "xp": lambda: X @ Pm + Pm @ X, "x3": lambda: X @ X @ X, "xpx": lambda: X @ Pm @ X}[name]()
+    return np.ascontiguousarray(m).astype(np.complex128)
+
+
+def baseline_force(ph: cfg.Physics, ex, strategy: str = "LQG", con_parameter: float = 0.0) -> torch.Tensor:
+    """float64 [M]: the analytic baseline controllers' force before it is clipped and rounded, F / omega (Fock) or
+    F / pi (grid), from ex(name) -> float64 [M] expectation values of `controller_operator`'s operators (torch tensors
+    on any device)."""
+    T = 1. / ph.n_con
+    if ph.fock:
+        if strategy != "LQG":
+            raise ValueError(f"the Fock families take only 'LQG', not {strategy!r}")
+        w = ph.omega
+        x, p = ex("x"), ex("p")
+        if ph.family == cfg.IHO:
+            F = -(x + p) * (1 + w * T + 0.5 * w * w * T * T) / (T + w * T * T / 2)
+        else:
+            F = -((x + p) + (p - x) * w * T) / T
+        F = F / w
+    else:
+        lam, mass = ph.lambda_, ph.mass
+        if strategy == "damping":
+            pp = ex("p") - 4. * lam * ex("x3") * T - T ** 2 * 2. * lam * 3. * ex("xpx") / mass
+            F = -pp / T * float(con_parameter)
+        elif strategy == "LQG":
+            k = lam * float(con_parameter)
+            x3 = ex("x3")
+            xq = ex("x") + ex("p") / mass * T - T ** 2 * 2. * lam * x3 / mass
+            pq = ex("p") - 4. * lam * x3 * T - T ** 2 * 2. * lam * 3. * ex("xpx") / mass
+            F = -(math.sqrt(k * mass) * xq + pq) / T
+        elif strategy == "semiclassical":
+            x = ex("x")
+            var = ex("x2") - x ** 2
+            F = (-torch.sqrt(2 * mass * (6 * lam * var + lam * x ** 2)) * x - ex("p")) / T
+        else:
+            raise ValueError(f"no strategy {strategy!r} (LQG, damping, semiclassical)")
+        F = F / math.pi
+    return F
+
+
+def baseline_slots(ph: cfg.Physics, ex, strategy: str = "LQG", con_parameter: float = 0.0) -> torch.Tensor:
+    """int32 [M] actions of the analytic baseline controllers: `baseline_force` clipped to +-f_max and rounded
+    half-to-even to the action grid, as the drivers do."""
+    F = baseline_force(ph, ex, strategy, con_parameter)
+    half = ph.n_actions // 2
+    unit = ph.f_max / half
+    return (torch.round(torch.clamp(F, -ph.f_max, ph.f_max) / unit) + half).to(torch.int32)

@@ -720,6 +720,58 @@ class Trainer:
             record()
         return {k: torch.stack(v) for k, v in out.items()}
 
+    def filtered_loop(self, me, n_control: int, *, eta: float, controller: Optional[tuple] = None,
+                      M: Optional[int] = None, seed: int = 0, source: str = "states") -> dict:
+        """The loop an observer with a detector of efficiency `eta` would run: M density matrices, each conditioned on
+        its own sampled measurement record (me.evolve_conditional), under the baseline
+        `controller` = (strategy, con_parameter) acting on rho itself (me.analytic_slots; None: the F = 0 slot).
+        source = 'states': the pure rho of the env's first M states (M None: all); 'ensemble': M copies (M None: 1) of
+        the ensemble density matrix of the env's current states. Control interval k takes the steps
+        first_step = k * env.ci of the records' streams. Returns device traces [n_control + 1, M] (entry 0: the start)
+        of 'x', 'x2', 'h', 'purity', 'boundary' (Fock also 'n') and 'slots' int32 [n_control, M]. The loop itself
+        waits on nothing; the setup may synchronise once (me.set_efficiency where `eta` is not the handle's already,
+        the first upload of the controllers' operators). The env and whatever evaluate() and open_loop() return are
+        untouched."""
+        if isinstance(n_control, bool) or not isinstance(n_control, int) or n_control < 0:
+            raise ValueError("Trainer.filtered_loop: n_control must be an int >= 0")
+        if source not in ("states", "ensemble"):
+            raise ValueError("Trainer.filtered_loop: source must be 'states' or 'ensemble'")
+        env = self.env
+        if M is not None and (isinstance(M, bool) or not isinstance(M, int) or M < 1
+                              or (source == "states" and M > env.B)):
+            raise ValueError("Trainer.filtered_loop: M must be an int >= 1" +
+                             (f" and <= the env's batch {env.B}" if source == "states" else ""))
+        if me.eta != float(eta):                       # (builds and uploads a table: may synchronise)
+            me.set_efficiency(eta)
+        if controller is None and me.zero_force_slot is None:
+            raise ValueError("Trainer.filtered_loop: the forces do not contain 0.0 and no controller is given")
+        if source == "states":
+            psi = env.psi[:env.B if M is None else M]
+            rho = (me.ensemble.scale * psi[:, :, None] * psi.conj()[:, None, :]).contiguous()
+        else:
+            rho = env.density_matrix(me.ensemble)[0][None].repeat(1 if M is None else M, 1, 1).contiguous()
+        count = int(rho.shape[0])
+        names = ("x", "x2", "h") + (("n",) if env.ph.fock else ())
+        out: dict = {k: [] for k in ("purity", "boundary", "slots") + names}
+
+        def record():
+            out["purity"].append((rho.real * rho.real + rho.imag * rho.imag).sum(dim=(-2, -1)))
+            out["boundary"].append(me.boundary_weight(rho))
+            for k in names:
+                out[k].append(me.expectations(rho, me.operator(k)))
+
+        record()
+        for k in range(n_control):
+            if controller is None:
+                slots = torch.full((count,), me.zero_force_slot, dtype=torch.int32, device=rho.device)
+            else:
+                slots = me.analytic_slots(rho, controller[0], float(controller[1]))
+            out["slots"].append(slots)
+            me.evolve_conditional(rho, env.ci, slots, seed=seed, first_step=k * env.ci)
+            record()
+        none = torch.empty((0, count), dtype=torch.int32, device=rho.device)
+        return {k: torch.stack(v) if v else none for k, v in out.items()}
+
     def _record_rho(self, ensemble, rho_every: int, valid, step: int):
         """One control step's entries of evaluate(ensemble=...): asynchronous, nothing waits."""
         rho = self.env.density_matrix(ensemble, mask=valid)[0]
@@ -809,6 +861,13 @@ def main(argv=None):
                     help="--open_loop_out: also wigner [T + 1, X, P], the Wigner function of the master equation's rho "
                          "per control interval, negativity [T + 1], its negative volume, and the axes wigner_x, "
                          "wigner_p (the key x there is <x>)")
+    ap.add_argument("--filtered_out", metavar="PATH", default=None,
+                    help="--test: the loop of an observer with detection efficiency --eta, one .npz: the conditional "
+                         "master equation's traces (x, x2, h, purity, boundary; ho / iho also n) [T + 1, M], slots "
+                         "[T, M] and t over --open_loop_steps control intervals from the first --filtered_M envs' "
+                         "states, under --control_strategy's baseline controller acting on rho (DQN: zero force)")
+    ap.add_argument("--eta", type=float, default=None, help="--filtered_out: the detection efficiency in (0, 1]")
+    ap.add_argument("--filtered_M", type=int, default=8, metavar="M")
     ap.add_argument("--control_strategy", choices=("DQN", "LQG", "damping", "semiclassical"), default="DQN",
                     help="other than DQN: one evaluation of the analytic baseline controller (ho / iho take LQG only, "
                          "the drivers' --LQG)")
@@ -818,6 +877,8 @@ def main(argv=None):
         ap.error(f"--control_strategy {args.control_strategy}: the Fock systems take only DQN or LQG")
     if args.open_loop_wigner and not args.open_loop_out:
         ap.error("--open_loop_wigner adds to the file of --open_loop_out, which is not given")
+    if args.filtered_out and args.eta is None:
+        ap.error("--filtered_out needs --eta")
     if args.levels_out and args.system in ("iho", "iqo"):
         ap.error(f"--levels_out: --system {args.system} has no bound levels (H is not bounded below)")
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
@@ -906,6 +967,15 @@ def main(argv=None):
             me.close()
             if olview is not None:
                 olview.close()
+        if args.filtered_out:
+            # before the evaluation moves the envs; it reads their states only
+            me = env.master_equation()
+            con = None if args.control_strategy == "DQN" else (args.control_strategy, args.con_parameter)
+            curve = trainer.filtered_loop(me, args.open_loop_steps, eta=args.eta, controller=con,
+                                          M=min(args.filtered_M, B), seed=seed)
+            np.savez(args.filtered_out, t=np.arange(args.open_loop_steps + 1) * (env.ci * ph.dt), eta=args.eta,
+                     **{k: v.cpu().numpy() for k, v in curve.items()})
+            me.close()
 
         def write_traces():
             if view is not None:

@@ -1104,6 +1104,68 @@ int qc_lindblad_evolve(qc_lindblad* h, void* rho, int32_t M, const int32_t* slot
 int qc_lindblad_congruence(qc_lindblad* h, const void* A, const double* g, const void* x, void* y, int32_t M);
 int qc_lindblad_take_errors(qc_lindblad* h);
 
+/* ---- conditional master equation: rho along a measurement record seen with detection efficiency eta ---------------
+ *   d rho = -i [H_F, rho] dt - (gamma / 4) [X, [X, rho]] dt + sqrt(eta gamma / 2) {X - <X>, rho} dW
+ * between the step kernels' pure states (eta = 1) and qc_lindblad_evolve (eta = 0). It works in qc_lindblad_evolve's
+ * basis (sigma = W^T rho W for Fock, taken there and back once per call; the grid itself otherwise) on its tables. With
+ * a = eta gamma dt / 2 and s = 1 / sqrt(4 a) (each formed in long double and rounded once), step n of matrix m is
+ *   1. sigma <- G^(1-eta) o (T_s sigma T_s^†): the congruence above, unchanged, with the table
+ *      G^(1-eta)_ij = exp(-gamma (1 - eta) dt (xi_i - xi_j)^2 / 4) (expl from the long double xi, gamma (1 - eta) in
+ *      long double) as g; no g at eta = 1.
+ *   2. the outcome (not in filtering mode): d_i = Re sigma_ii where that is not below 0, else 0 (a NaN stays); c_i its
+ *      inclusive prefix sums; I = min { i : c_i > u c_(N-1) } (N - 1 where no c_i is: u = 1 after rounding);
+ *      y = fma(z, s, xi_I). That samples p(y) = sum_i sigma_ii sqrt(2 a / pi) exp(-2 a (xi_i - y)^2) exactly; y is in
+ *      the units of the step kernels' measurement outcome q: E y = Tr(sigma X), noise variance 1 / (2 eta gamma dt).
+ *   3. e_i = (xi_i - y)^2, e0 = min_i e_i, w_i = exp(-(a (e_i - e0))), Z = sum_i (w_i w_i) d_i, v_i = w_i / sqrt(Z),
+ *      sigma_ij <- (v_i v_j) sigma_ij with the product v_i v_j formed first (a Hermitian-by-bit-pattern sigma with a
+ *      +0.0 diagonal imaginary part stays so). Tr sigma = 1 after every step up to rounding; nothing accumulates.
+ * The average over y of 2-3 is G^eta o sigma, so the mean over records of n steps is (G o T . T^†)^n sigma_0 exactly:
+ * every step is an exact quantum instrument. At eta = 1 a pure sigma stays pure. The input is ASSUMED Hermitian, as
+ * qc_lindblad_congruence assumes it.
+ * The order of the sums c and Z (one routine, a function of N alone): indices in chunks of 256 ascending; inside a
+ * chunk the doubling t_i <- t_i + t_(i-s) for s = 1, 2, 4 .. 128, every i >= s of the chunk at once, elements past N
+ * entering as +0; c_i = carry + t_i with carry the c of the previous chunk's last element (+0 for the first); Z is the
+ * last element of the sums of (w_i w_i) d_i. min is exact. Two launches per step after the congruence's two
+ * (k_filter_draw: one workgroup per matrix; k_filter_apply: one element per thread); one device copy of rho into a
+ * buffer of the handle before the first step and one launch after the last (below). No atomics, nothing waits on the
+ * host.
+ * Random numbers: Philox4x32-10 keyed by seed at counter (step_lo, step_hi, stream id, tag), step = first_step + n,
+ * stream id = streams[m] (device int32 [M]; NULL: m): u = ((w0 << 32 | w1) >> 11 + 0.5) 2^-53 of the block at tag
+ * 0x500, z = the step kernels' normal r0 of the block at tag 0x501. Nothing is stored between calls: a matrix's
+ * trajectory depends on (seed, stream id, step) alone, not on M or its place in the batch, and n steps in one call give
+ * the record of two calls of n / 2 with first_step bit for bit, and for the grid families the same rho bit for bit (a
+ * Fock rho goes to sigma and back once per call: two calls round the two basis changes once more and agree with one
+ * call within rounding). draws (device [n_steps][M][2]: u, z) overrides Philox. Filtering
+ * mode: record_in (device [n_steps][M]) supplies y and nothing is drawn; record_in together with draws is refused.
+ * record_out (device [n_steps][M] or NULL) receives y.
+ * qc_lindblad_filter_draws (host only) gives the (u, z) the device draws at (seed, stream id, step): u exactly, z
+ * within rounding (< 1e-15) of the device's.
+ * A matrix that cannot be stepped (c_(N-1), y or Z not finite, c_(N-1) or Z not > 0; in filtering mode Z = 0 means
+ * the record contradicts the state) is left as the call found it, bit for bit (the launch after the last step writes
+ * the copy back), its record entries from that step on are NaN, and it raises a second bit of the handle's error
+ * flag, which qc_lindblad_take_errors reports once with its own text. A slot outside [0, J) is handled as
+ * qc_lindblad_evolve handles it.
+ * qc_lindblad_set_efficiency(h, eta), eta in (0, 1] and the handle's gamma > 0 (refused with a text otherwise),
+ * builds G^(1-eta) on the host, waits for the handle's stream and uploads it (it may synchronise).
+ * qc_lindblad_efficiency gives eta, -1 while unset. qc_lindblad_evolve_conditional's limits are
+ * qc_lindblad_evolve's; first_step >= 0; n_steps = 0 launches nothing; a call before qc_lindblad_set_efficiency is
+ * refused before the device is touched; every pointer except rho may be NULL. */
+int qc_lindblad_set_efficiency(qc_lindblad* h, double eta);
+/* *eta: the efficiency, -1 while unset */
+int qc_lindblad_efficiency(const qc_lindblad* h, double* eta);
+/* rho: device [M][N][N] complex128, in place; slots, streams: device int32 [M] or NULL; draws: device
+ * [n_steps][M][2] or NULL; record_in, record_out: device [n_steps][M] or NULL */
+int qc_lindblad_evolve_conditional(qc_lindblad* h, void* rho, int32_t M, const int32_t* slots, int32_t default_slot,
+                                   int32_t n_steps, uint64_t seed, const int32_t* streams, int64_t first_step,
+                                   const double* draws, const double* record_in, double* record_out);
+/* xi: device [N]: a copy of the handle's own eigenvalues of X, asynchronous on the bound stream */
+int qc_lindblad_xi(qc_lindblad* h, double* xi);
+/* host only: the table qc_lindblad_set_efficiency uploads (the unit matrix at eta = 1, where it is not read), g host
+ * [N][N]; refusals as qc_lindblad_tables' and qc_lindblad_set_efficiency's, with a text (qc_lindblad_last_error(NULL)) */
+int qc_lindblad_efficiency_table(const qc_params* p, double dt, double gamma, double eta, double* g);
+/* host only */
+int qc_lindblad_filter_draws(uint64_t seed, uint32_t stream, uint64_t step, double* u, double* z);
+
 /* ---- step server: the reference's process model on one GPU ------------------------------------------------
  * The drivers run 30-40 actor processes, each with its own `simulation` module stepping ONE env per call
  * (IHO/main_parallel.py:345-359, :264). A step server owns one handle of batch max_clients (env e = client slot
